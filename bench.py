@@ -14,6 +14,8 @@ candidates, which are resident in HBM before the timed region starts.
           reported by itself ("gather"); if it fails the run fails.  Rank 0 then repeats its own share alone
           ("one_gpu_same_share") so that the line shows what a GPU does on that share with the other ranks idle.
   --workload config2|config4 and --fusions/--reads/--lq/--lr override the defaults (--fusions is the whole job).
+  --steps K runs exactly K timed steps ("ms_per_step" is one of them); without it the default count is raised until the
+  timed region lasts MIN_TIMED_S.  --dump-outputs DIR writes the records of the last timed step (see dump_outputs).
 
     python bench.py                       # N = 1
     python bench.py --gpus 2              # starts its own 2 ranks (children, before this process touches a GPU)
@@ -34,7 +36,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-MIN_TIMED_S = 3.0          # the timed region is at least this long whatever --steps says ("steps" reports what ran)
+MIN_TIMED_S = 3.0          # without --steps the timed region is at least this long ("steps" reports what ran)
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together stay below this
+DUMP_SEED = 20241015       # the fixed sample of records --dump-outputs writes when the job has more than fit
 PROFILE_DIR = os.path.join(ROOT, "profiles", "r04")
 WORKLOADS = {"config2": dict(fusions=10000, reads=100, lq=76, lr=389),
              "config4": dict(fusions=1000000, reads=200, lq=100, lr=390)}
@@ -243,6 +247,56 @@ def one_shot(ctx, batch, reps=5, stream_batches=12, depth=3):
                     "single_call = one dsa_align_batch, nothing overlapped" % (stream_batches, n_pairs, depth)}
 
 
+def dump_outputs(out_dir, parts):
+    """--dump-outputs: the records of the timed path's last step, as a caller receives them (one row per record, job order,
+    pair numbers job-wide), written column by column as DIR/<field>.npy in float64 (exact for int32), beside
+    DIR/sample_index.npy (each row's position among all records of the step) and DIR/n_records.npy.  If all records
+    do not fit into DUMP_BYTES, a fixed sample of them (seed DUMP_SEED) is written.  parts: (n_records, fetch) per upload
+    in job order; fetch() returns that upload's records as int32 rows [n, RECORD_WORDS] (numpy or a torch tensor)."""
+    import numpy as np
+    from defuse_amd import dsa
+    fields = dsa.RECORD_DTYPE.names
+    n_total = int(sum(n for n, _ in parts))
+    cap = (DUMP_BYTES - (1 << 16)) // (8 * (len(fields) + 1))
+    if n_total <= cap:
+        idx = np.arange(n_total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n_total, cap, replace=False))
+    rows, off = [], 0
+    for n, fetch in parts:
+        sel = idx[(idx >= off) & (idx < off + n)] - off
+        if len(sel):
+            r = fetch()
+            if len(r) != n:
+                raise RuntimeError("--dump-outputs: %d records fetched, %d expected" % (len(r), n))
+            if hasattr(r, "cpu"):
+                import torch
+                r = r[torch.from_numpy(sel).to(r.device)].cpu().numpy()
+            else:
+                r = np.asarray(r)[sel]
+            rows.append(r.astype(np.int64))
+        off += n
+    rows = np.concatenate(rows) if rows else np.zeros((0, len(fields)), dtype=np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, f in enumerate(fields):
+        np.save(os.path.join(out_dir, f + ".npy"), rows[:, k].astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "n_records.npy"), np.array([n_total], dtype=np.float64))
+    return {"dir": out_dir, "records": n_total, "written": int(len(idx)), "sampled": bool(len(idx) < n_total), "seed": DUMP_SEED}
+
+
+def share_output_parts(share):
+    """The records of a share's last run per upload, for dump_outputs (pair numbers made job-wide)."""
+    import numpy as np
+    from defuse_amd import shard
+
+    def fetch(ctx, base):
+        r = ctx.download().view(np.int32).reshape(-1, shard.RECORD_WORDS).copy()
+        r[:, -1] += base
+        return r
+    return [(int(c.timing().n_records), lambda c=c, b=b: fetch(c, b)) for c, b in zip(share.ctxs, share.pair_base)]
+
+
 def ctx_device(ctx):
     return getattr(ctx, "device", 0)
 
@@ -301,7 +355,7 @@ class Share:
             ctx.close()
 
 
-def gather_job(share, rank, world, backend, barrier, dump=None):
+def gather_job(share, rank, world, backend, barrier, dump=None, outputs_dir=None):
     """The final gather of the job's records on rank 0 (defuse_amd/shard.py:gather_records), once, after the timed steps:
     every upload's records are copied device -> device into one tensor per rank (pair numbers made job-wide), then one
     all_gather of the counts and one group of exact-size isend/irecv.  Any failure propagates (non-zero exit)."""
@@ -326,7 +380,7 @@ def gather_job(share, rank, world, backend, barrier, dump=None):
     allb = torch.zeros(2 * world, dtype=torch.int64, device=rows.device)
     torch.distributed.all_gather_into_tensor(allb, bounds)
     if rank != 0:
-        return None
+        return None, None
     total = sum(counts)
     if out.shape[0] != total:
         raise RuntimeError("gather: %d records arrived, %d announced" % (out.shape[0], total))
@@ -341,9 +395,10 @@ def gather_job(share, rank, world, backend, barrier, dump=None):
     if dump:
         import numpy as np
         np.save(dump, out.cpu().numpy())
-    return {"ms": ms, "records": total, "bytes_moved": nbytes, "GB/s": nbytes / (ms * 1e-3) / 1e9, "verified": True,
-            "backend": "rccl" if backend == "nccl" else backend, "included_in_value": False, "times_per_job": 1,
-            "pattern": "all_gather of counts + grouped isend/irecv, exact sizes, peers -> rank 0"}
+    dumped = dump_outputs(outputs_dir, [(total, lambda: out)]) if outputs_dir else None
+    return dumped, {"ms": ms, "records": total, "bytes_moved": nbytes, "GB/s": nbytes / (ms * 1e-3) / 1e9, "verified": True,
+                    "backend": "rccl" if backend == "nccl" else backend, "included_in_value": False, "times_per_job": 1,
+                    "pattern": "all_gather of counts + grouped isend/irecv, exact sizes, peers -> rank 0"}
 
 
 def spawn_ranks(args):
@@ -379,7 +434,8 @@ def spawn_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="default 100 at config 2, 20 at config 4")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps, exactly; default 100 at config 2, 20 at config 4, "
+                    "raised until the timed region lasts MIN_TIMED_S")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None, help="default: config2 at N = 1, config4 (strong scaling) at N > 1")
     ap.add_argument("--fusions", type=int, default=None, help="fusions of the WHOLE job")
@@ -389,10 +445,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sensitivity", action="store_true", help="skip the secondary workload-mix legs (N = 1)")
     ap.add_argument("--dump-records", default=None, help="N > 1: rank 0 writes the gathered records of the job (numpy .npy) here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the records of the last one as DIR/<field>.npy (float64, at most 64 MB: "
+                         "a fixed sample of a larger output)")
     ap.add_argument("--profile-run", action="store_true",
                     help="for rocprofv3 passes: exactly --steps timed steps and nothing else (no minimum duration, no resident re-run, "
                          "no one-shot leg, no CPU baseline)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1 and os.environ.get("DEFUSE_BENCH_GATHER", "1") == "0":
+        ap.error("--dump-outputs at N > 1 writes the gathered records: it needs the gather (DEFUSE_BENCH_GATHER=0 is set)")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -489,12 +552,15 @@ def main():
             raise SystemExit("bench.py: GPU records differ from the oracle on the sample")
     steps_requested = steps
     elapsed, stage = timed(steps)
-    if elapsed < MIN_TIMED_S and not args.profile_run:
+    if elapsed < MIN_TIMED_S and args.steps is None and not args.profile_run:
         # a timed region shorter than MIN_TIMED_S does not stand: the same loop again with as many steps as fill it
         # (every rank derives the same count from the reduced clock)
         steps = int(steps * MIN_TIMED_S * 1.15 / max(elapsed, 1e-6)) + 1
         elapsed, stage = timed(steps)
     fill_ms, pack_ms, finish_ms, plan_ms, launches = stage
+    dumped = None
+    if args.dump_outputs and world == 1:          # the records of the last timed step, before anything else runs on the share
+        dumped = dump_outputs(args.dump_outputs, share_output_parts(share))
     # the same resident, already planned batch run again without its planning: round 2's number, for comparison only
     k_rerun = max(3, steps // 4) if not args.profile_run else 1
     rerun_s, _ = timed(k_rerun, plan=False)
@@ -511,7 +577,9 @@ def main():
         if os.environ.get("DEFUSE_BENCH_GATHER", "1") != "0":
             if os.environ.get("DEFUSE_BENCH_TEST_EXIT_RANK") == str(rank):  # tests: a rank that dies before the exchange
                 os._exit(3)
-            gather = gather_job(share, rank, world, backend, barrier, args.dump_records)       # raises on failure: the run fails
+            # raises on failure: the run fails.  The gathered records are those of the resident re-run, which
+            # recomputes the last timed step's inputs unchanged.
+            dumped, gather = gather_job(share, rank, world, backend, barrier, args.dump_records, args.dump_outputs)
         # rank 0 alone on its share, the other ranks idle at the barrier
         if rank == 0:
             k = max(3, steps // 4)
@@ -605,6 +673,8 @@ def main():
                                                        "(`bench.py --gpus 1 --workload config4` measures exactly that)" % world}
         if base is not None:
             out["cpu_baseline"] = base
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and len(share.ctxs) == 1 and not args.profile_run and not multi and not args.no_sensitivity:
             out["sensitivity"] = sensitivity(dsa, synth, share.ctxs[0], workload, share.first_batch)
         if world == 1 and len(share.ctxs) == 1 and not args.profile_run:

@@ -21,7 +21,8 @@ def run_bench(tmp_path, extra_env=None, timeout=900):
     env.update(extra_env or {})
     dump = str(tmp_path / "records.npy")
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--fusions", str(FUSIONS), "--steps", "3",
-                           "--warmup", "1", "--dump-records", dump], capture_output=True, text=True, env=env, timeout=timeout), dump
+                           "--warmup", "1", "--dump-records", dump, "--dump-outputs", str(tmp_path / "outputs")],
+                          capture_output=True, text=True, env=env, timeout=timeout), dump
 
 
 def test_two_ranks_share_one_card_and_gather(built, tmp_path):
@@ -32,7 +33,20 @@ def test_two_ranks_share_one_card_and_gather(built, tmp_path):
     assert line["config"]["aligns_per_step_this_gpu"] == FUSIONS // 2 * READS
     g = line["gather"]
     assert g["verified"] is True and g["backend"] == "gloo" and g["records"] == line["config"]["job_records"] > FUSIONS * READS
-    assert line["steps"] >= 3 and line["ms_per_step"] * line["steps"] >= 900          # the timed region is at least a second
+    assert line["steps"] == line["steps_requested"] == 3 and line["ms_per_step"] > 0     # --steps is the number of timed steps
+    # --dump-outputs: the gathered records, column by column in float64; more than fit into 64 MB, so a sample of them
+    import numpy as np
+    recs = np.load(dump).reshape(-1, 10)
+    outs = tmp_path / "outputs"
+    assert line["dump_outputs"]["records"] == len(recs) and line["dump_outputs"]["sampled"]
+    assert sum(os.path.getsize(str(outs / f)) for f in os.listdir(str(outs))) <= 64 * 10 ** 6
+    assert int(np.load(str(outs / "n_records.npy"))[0]) == len(recs)
+    idx = np.load(str(outs / "sample_index.npy")).astype(np.int64)
+    assert len(idx) == line["dump_outputs"]["written"] and np.all(np.diff(idx) > 0) and idx[-1] < len(recs)
+    for k, name in enumerate(("fusion_id", "frag", "read_end", "revcomp", "ref_first", "ref_second", "read_first", "read_second",
+                              "score", "pair_idx")):
+        col = np.load(str(outs / (name + ".npy")))
+        assert col.dtype == np.float64 and np.array_equal(col, recs[idx, k].astype(np.float64)), name
     # the gathered records against the oracle, on the first fusions of either rank's share (a process of its own: torch's HIP
     # runtime has to come up before the library's, and this pytest process already holds the library)
     code = '''
