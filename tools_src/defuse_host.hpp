@@ -33,6 +33,7 @@
 #include <set>
 #include <sstream>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <unordered_map>
 #include <unordered_set>
@@ -1024,6 +1025,7 @@ public:
         std::ifstream in(fai.c_str(), std::ios::binary);
         if (!in.good()) {
             std::cerr << "[fai_load] build FASTA index." << std::endl;
+            built_index_ = true;
             build(fasta, fai);
             in.open(fai.c_str(), std::ios::binary);
             if (!in.good()) die("[fai_load] fail to open FASTA index.");
@@ -1053,6 +1055,8 @@ public:
         if (fd_ >= 0) close(fd_);
     }
     FastaIndex() = default;
+    // Open found no index, said so on stderr and wrote one
+    bool built_index() const { return built_index_; }
     FastaIndex(const FastaIndex&) = delete;
     FastaIndex& operator=(const FastaIndex&) = delete;
 
@@ -1113,6 +1117,7 @@ public:
 private:
     const char* map_ = nullptr;
     size_t map_n_ = 0;
+    bool built_index_ = false;
     struct Entry { long long len = 0, offset = 0; int line_blen = 0, line_len = 0; };
     static void build(const std::string& fasta, const std::string& fai)
     {
@@ -1326,10 +1331,8 @@ inline bool ParseTranscriptID(const std::string& id, std::string& gene, std::str
 }
 
 // tools/Parsers.cpp:211-264
-inline std::map<int, std::vector<Location>> ReadAlignRegionPairs(const std::string& filename)
+inline std::map<int, std::vector<Location>> ReadAlignRegionPairs(std::istream& in)
 {
-    std::ifstream in(filename.c_str());
-    if (!in.good()) die("Error: Unable to open align region pairs file " + filename);
     std::map<int, std::vector<Location>> pairs;
     std::string line;
     while (std::getline(in, line)) {
@@ -1354,16 +1357,41 @@ inline std::map<int, std::vector<Location>> ReadAlignRegionPairs(const std::stri
     }
     return pairs;
 }
+inline std::map<int, std::vector<Location>> ReadAlignRegionPairs(const std::string& filename)
+{
+    std::ifstream in(filename.c_str());
+    if (!in.good()) die("Error: Unable to open align region pairs file " + filename);
+    return ReadAlignRegionPairs(in);
+}
 
 // ---------------------------------------------------------------------------------------------
 // SplitAlignmentTask geometry: tools/SplitAlignment.cpp:31-175, :637-655, :657-686.
 // ---------------------------------------------------------------------------------------------
+// A task's reference sequence: bytes of its own (the cold set-up cuts them out of the FASTA) or a view of bytes that outlive
+// the task (a task-cache hit points into the mapped cache file instead of copying a hundred megabytes, task_cache.hpp).
+class SeqText {
+public:
+    std::string& own() { p_ = nullptr; n_ = 0; return s_; }          // the bytes of its own, to be written
+    void view(const char* p, size_t n) { s_.clear(); p_ = p; n_ = n; }
+    const char* data() const { return p_ ? p_ : s_.data(); }
+    size_t size() const { return p_ ? n_ : s_.size(); }
+    size_t length() const { return size(); }
+    std::string_view sv() const { return std::string_view(data(), size()); }
+    std::string substr(size_t pos, size_t n = std::string::npos) const { return std::string(sv().substr(pos, n)); }   // (throws as std::string's)
+    bool operator==(const SeqText& o) const { return sv() == o.sv(); }
+
+private:
+    std::string s_;
+    const char* p_ = nullptr;
+    size_t n_ = 0;
+};
+
 struct SplitAlignmentTask {
     int mFusionID = 0;
     std::string mAlignRefName[2];
     int mAlignStrand[2] = {0, 0};
     int mSplitAlignSeqStart[2] = {0, 0}, mSplitAlignSeqLength[2] = {0, 0}, mSplitSeqStrand[2] = {0, 0};
-    std::string mSplitAlignSeq[2], mSplitRemainderSeq[2];
+    SeqText mSplitAlignSeq[2], mSplitRemainderSeq[2];
     std::vector<Location> mMateRegions[2];
 
     static void CalculateBreakRegion(int minRead, int maxRead, int maxFrag, int alignStart, int alignEnd, int strand, int& breakStart, int& breakLength)
@@ -1399,16 +1427,16 @@ struct SplitAlignmentTask {
                 mSplitAlignSeqStart[ce] = breakStart - breakLength + 1;
                 mSplitAlignSeqLength[ce] = breakLength + maxReadLength;
             }
-            reference.Get(refName, refSeqStrand, mSplitAlignSeqStart[ce], mSplitAlignSeqLength[ce], mSplitAlignSeq[ce]);
-            mSplitRemainderSeq[ce].clear();
+            reference.Get(refName, refSeqStrand, mSplitAlignSeqStart[ce], mSplitAlignSeqLength[ce], mSplitAlignSeq[ce].own());
+            mSplitRemainderSeq[ce].own().clear();
             if (strand == PlusStrand) {
                 if (alignStart < mSplitAlignSeqStart[ce]) {
                     int rs = alignStart, rl = mSplitAlignSeqStart[ce] - 1 - alignStart + 1;
-                    reference.Get(refName, refSeqStrand, rs, rl, mSplitRemainderSeq[ce]);
+                    reference.Get(refName, refSeqStrand, rs, rl, mSplitRemainderSeq[ce].own());
                 }
             } else if (alignEnd > mSplitAlignSeqStart[ce] + mSplitAlignSeqLength[ce] - 1) {
                 int rs = mSplitAlignSeqStart[ce] + mSplitAlignSeqLength[ce], rl = alignEnd - rs + 1;
-                reference.Get(refName, refSeqStrand, rs, rl, mSplitRemainderSeq[ce]);
+                reference.Get(refName, refSeqStrand, rs, rl, mSplitRemainderSeq[ce].own());
             }
             std::string chromosome, gene, transcript;
             int genomeStrand, genomeBreakStart;
@@ -1436,9 +1464,12 @@ struct SplitAlignmentTask {
     }
 };
 
+// *clean (when given): the set-up printed nothing (no index built, no task refused its input) — only such a set-up may be
+// kept in the task cache (task_cache.hpp), so that a later hit never hides a message
 inline std::map<int, SplitAlignmentTask> CreateTasks(const std::string& fasta, const std::string& exonsFile, double fragMean,
                                                      double fragStdDev, int minRead, int maxRead,
-                                                     const std::map<int, std::vector<Location>>& regions, unsigned threads = 0)
+                                                     const std::map<int, std::vector<Location>>& regions, unsigned threads = 0,
+                                                     bool* clean = nullptr)
 {
     const bool timing = std::getenv("DEFUSE_TIMING") != nullptr;
     auto clock_now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1465,11 +1496,14 @@ inline std::map<int, SplitAlignmentTask> CreateTasks(const std::string& fasta, c
     lap("task table");
     // the fusions are independent and everything they read (index, exon tables, the FASTA through pread) is read-only
     const unsigned n = work.size() < 64 ? 1u : (threads ? threads : host_threads());
+    std::atomic<bool> refused{false};
     run_threads(n, [&](unsigned t) {
         for (size_t i = t; i < work.size(); i += n)
-            work[i].first->Initialize(ids[i], *work[i].second, reference, exons, fragMean, fragStdDev, minRead, maxRead);
+            if (!work[i].first->Initialize(ids[i], *work[i].second, reference, exons, fragMean, fragStdDev, minRead, maxRead))
+                refused.store(true, std::memory_order_relaxed);
     });
     lap("windows and mate regions");
+    if (clean) *clean = !reference.built_index() && !refused.load();
     return tasks;
 }
 
@@ -1540,6 +1574,75 @@ public:
             std::sort(ids.begin(), ids.end());
             ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
         }
+    }
+
+    // the ids Add was given, in the order of the Adds
+    const std::vector<int>& ids() const { return ids_; }
+
+    // The finished table as bytes (the task cache keeps it, task_cache.hpp) and back.  Load checks every index the lookups
+    // follow and refuses (false, the object left empty) what does not hold together.
+    void Save(std::string& out) const
+    {
+        auto put = [&](const void* p, size_t n) { out.append((const char*)p, n); };
+        auto put_u64 = [&](uint64_t v) { put(&v, 8); };
+        auto put_vec = [&](const auto& v) { put_u64(v.size()); put(v.data(), v.size() * sizeof(v[0])); };
+        put_u64((uint64_t)spacing_);
+        for (int s = 0; s < 2; ++s) {
+            std::vector<std::pair<std::string, int>> names(ref_index_[s].begin(), ref_index_[s].end());
+            std::sort(names.begin(), names.end());              // (the same bytes whichever way the map iterates)
+            put_u64(names.size());
+            for (const auto& nm : names) { put_u64(nm.first.size()); put(nm.first.data(), nm.first.size()); put_u64((uint64_t)(uint32_t)nm.second); }
+        }
+        put_u64(refs_.size());
+        for (const RefBins& rb : refs_) { put_u64((uint64_t)(uint32_t)rb.first_bin); put_vec(rb.start); }
+        put_vec(flat_);
+        put_vec(ids_);
+        put_vec(regions_);
+    }
+    bool Load(const char* p, size_t n)
+    {
+        const char* const end = p + n;
+        auto get = [&](void* dst, size_t k) { if ((size_t)(end - p) < k) return false; std::memcpy(dst, p, k); p += k; return true; };
+        auto get_u64 = [&](uint64_t& v) { return get(&v, 8); };
+        auto get_vec = [&](auto& v) {
+            uint64_t k;
+            if (!get_u64(k) || k > (uint64_t)(end - p) / sizeof(v[0])) return false;
+            v.resize((size_t)k);
+            return get(v.data(), (size_t)k * sizeof(v[0]));
+        };
+        auto fail = [&] { *this = BinnedLocations(spacing_); return false; };
+        *this = BinnedLocations(spacing_);
+        uint64_t v, k;
+        if (!get_u64(v) || v != (uint64_t)spacing_) return fail();
+        std::vector<int> ref_of;                                // every (strand, name) entry's ref, checked below
+        for (int s = 0; s < 2; ++s) {
+            if (!get_u64(k) || k > (uint64_t)(end - p) / 16) return fail();
+            for (uint64_t x = 0; x < k; ++x) {
+                uint64_t len;
+                if (!get_u64(len) || len > (uint64_t)(end - p)) return fail();
+                std::string name(p, (size_t)len);
+                p += len;
+                if (!get_u64(v) || v > INT_MAX) return fail();
+                ref_index_[s].emplace(std::move(name), (int)v);
+                ref_of.push_back((int)v);
+            }
+        }
+        if (!get_u64(k) || k > (uint64_t)(end - p) / 16) return fail();
+        refs_.resize((size_t)k);
+        for (RefBins& rb : refs_) {
+            if (!get_u64(v) || !get_vec(rb.start)) return fail();
+            rb.first_bin = (int)(uint32_t)v;
+        }
+        if (!get_vec(flat_) || !get_vec(ids_) || !get_vec(regions_) || p != end || ids_.size() != regions_.size()) return fail();
+        for (int r : ref_of)
+            if ((size_t)r >= refs_.size()) return fail();
+        for (const RefBins& rb : refs_)
+            for (size_t x = 0; x < rb.start.size(); ++x)
+                if (rb.start[x] > flat_.size() || (x > 0 && rb.start[x] < rb.start[x - 1])) return fail();
+        for (int idx : flat_)
+            if (idx < 0 || (size_t)idx >= ids_.size()) return fail();
+        finished_ = true;
+        return true;
     }
 
 private:

@@ -39,6 +39,7 @@
 
 #include "../include/defuse_dsa.h"
 #include "evaluate.hpp"
+#include "task_cache.hpp"
 
 using namespace defuse;
 
@@ -429,7 +430,17 @@ int main(int argc, char* argv[])
         if (!rf.close_file()) die("Error: failed writing " + cmd.str("regions"));
         stage("clusters -> regions file");
     }
-    const std::map<int, std::vector<Location>> regions = ReadAlignRegionPairs(cmd.str("regions"));
+    // threads per team: DEFUSE_THREADS, else up to 16 (the teams replace a thread start per pass by a wake-up, so sixteen pay
+    // where eight used to be the limit: ten million candidates in 1.10 s instead of 1.33 s on a 16-core GPU box)
+    const unsigned nThreads = std::getenv("DEFUSE_THREADS") ? host_threads() : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    // DEFUSE_DSA_TASK_CACHE=1 (task_cache.hpp): the tasks and their bins from "<regions>.dsatasks" when its key matches; not in
+    // fused mode, whose process writes the regions file itself
+    task_cache::SetUp cache;
+    cache.on = opt_clusters.empty() && task_cache::enabled();
+    cache.timing = timing;
+    cache.tag = "[dosplitalign]";
+    cache.path = task_cache::path_for(cmd.str("regions"));
+    const std::map<int, std::vector<Location>> regions = cache.read_regions(cmd.str("regions"), nThreads);
     stage("regions");
 
     if (!have_worker && !regions.empty()) start_worker(regions.size());
@@ -464,9 +475,6 @@ int main(int argc, char* argv[])
         }
     };
 
-    // threads per team: DEFUSE_THREADS, else up to 16 (the teams replace a thread start per pass by a wake-up, so sixteen pay
-    // where eight used to be the limit: ten million candidates in 1.10 s instead of 1.33 s on a 16-core GPU box)
-    const unsigned nThreads = std::getenv("DEFUSE_THREADS") ? host_threads() : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     // The two FASTQ files are read by a team of their own while the main thread sets the tasks up (FASTA index — built and
     // written when it is missing —, exon table, windows) and parses the first round of SAM text: independent inputs.  Whatever
     // the reads' side has to say is held back until the tasks are done, so that messages and exits come in the reference's
@@ -487,25 +495,30 @@ int main(int argc, char* argv[])
         std::thread& th;
         ~Joiner() { if (th.joinable()) th.join(); }
     } reads_joiner{reads_thread};
-    std::map<int, SplitAlignmentTask> tasks = CreateTasks(cmd.str("fasta"), cmd.str("exons"), cmd.real("ufrag"), cmd.real("sfrag"),
-                                                         cmd.integer("minread"), cmd.integer("maxread"), regions, nThreads);
-    stage("  tasks (windows from the FASTA, mate regions)");
-
     // SplitReadRealigner::AddTask (tools/SplitAlignment.cpp:236-251): 2000 bp bins over the mate regions
     // The ids in the bins are task ORDINALS (position in ascending fusion id order) rather than fusion ids: they sort the
     // same way, and per-batch tables indexed by them replace hash lookups.
     BinnedLocations binned(2000);
+    std::map<int, SplitAlignmentTask> tasks = cache.tasks(cmd.str("fasta"), cmd.str("exons"), cmd.real("ufrag"), cmd.real("sfrag"),
+                                                          cmd.integer("minread"), cmd.integer("maxread"), regions, nThreads, &binned);
+    stage("  tasks (windows from the FASTA, mate regions)");
+    bool bin = !cache.have_binned;
+    if (!bin)                                  // bins from the cache: every id they hold names a task
+        for (int id : binned.ids())
+            if ((size_t)(id & 0x7FFFFFFF) >= tasks.size()) { bin = true; binned = BinnedLocations(2000); break; }
     std::vector<const SplitAlignmentTask*> task_of;
     std::vector<int> fusion_id_of;
     for (const auto& kv : tasks) {
         if (kv.first < 0) die("Error: negative fusion id " + std::to_string(kv.first));
-        for (int ce = 0; ce <= 1; ++ce)
-            for (const Location& loc : kv.second.mMateRegions[ce]) binned.Add(pack_id((int)task_of.size(), ce), loc);
+        if (bin)
+            for (int ce = 0; ce <= 1; ++ce)
+                for (const Location& loc : kv.second.mMateRegions[ce]) binned.Add(pack_id((int)task_of.size(), ce), loc);
         task_of.push_back(&kv.second);
         fusion_id_of.push_back(kv.second.mFusionID);
     }
-    binned.Finish();
+    if (bin) binned.Finish();
     const size_t n_tasks = task_of.size();
+    cache.keep(tasks, &binned, nThreads);
     stage("fasta index + exons + windows");
     bool reads_reported = false;
     auto report_reads = [&] {                // once, before the first candidate is taken up

@@ -5,6 +5,7 @@
 // no DP and is I/O bound.  Ties between equally supported breakpoints go to the
 // lexicographically smallest refSplit (canonical order of SURVEY.md 8(c)).
 #include "evaluate.hpp"
+#include "task_cache.hpp"
 
 using namespace defuse;
 
@@ -24,9 +25,16 @@ int main(int argc, char* argv[])
     cmd.add("p", "predalign", "Prediction Split Alignments Filename", "string");
     cmd.parse(argc, argv);
 
-    const std::map<int, std::vector<Location>> regions = ReadAlignRegionPairs(cmd.str("regions"));
-    std::map<int, SplitAlignmentTask> tasks = CreateTasks(cmd.str("fasta"), cmd.str("exons"), cmd.real("ufrag"), cmd.real("sfrag"),
-                                                         cmd.integer("minread"), cmd.integer("maxread"), regions);
+    // DEFUSE_DSA_TASK_CACHE=1: the tasks from "<regions>.dsatasks" when its key matches (task_cache.hpp)
+    task_cache::SetUp cache;
+    cache.on = task_cache::enabled();
+    cache.timing = std::getenv("DEFUSE_TIMING") != nullptr;
+    cache.tag = "[evalsplitalign]";
+    cache.path = task_cache::path_for(cmd.str("regions"));
+    const std::map<int, std::vector<Location>> regions = cache.read_regions(cmd.str("regions"), host_threads());
+    std::map<int, SplitAlignmentTask> tasks = cache.tasks(cmd.str("fasta"), cmd.str("exons"), cmd.real("ufrag"), cmd.real("sfrag"),
+                                                          cmd.integer("minread"), cmd.integer("maxread"), regions, host_threads(), nullptr);
+    cache.keep(tasks, nullptr, host_threads());
 
     // The alignment file is mapped and cut into one piece per host thread at group boundaries (a group = a run of lines
     // with one fusion id, as ReadSortedAlignments forms them); the pieces are evaluated side by side and their three texts

@@ -97,8 +97,11 @@ inline void EvaluateGroup(const SplitAlignmentTask& task, const std::vector<Spli
             if (a.refSplit == best) kept.push_back(&a);
         if (!(best.first <= (int)task.mSplitAlignSeq[0].length())) debug_check_failed("bestSplit.first <= mSplitAlignSeq[0].length()");
         if (!(best.second + 1 < (int)task.mSplitAlignSeq[1].length())) debug_check_failed("bestSplit.second + 1 < mSplitAlignSeq[1].length()");
-        sequence = task.mSplitRemainderSeq[0] + task.mSplitAlignSeq[0].substr(0, best.first) + "|" +
-                   task.mSplitAlignSeq[1].substr(best.second + 1) + task.mSplitRemainderSeq[1];
+        sequence.assign(task.mSplitRemainderSeq[0].sv());
+        sequence += task.mSplitAlignSeq[0].sv().substr(0, best.first);
+        sequence += '|';
+        sequence += task.mSplitAlignSeq[1].sv().substr(best.second + 1);
+        sequence += task.mSplitRemainderSeq[1].sv();
         breakPos[0] = task.mSplitSeqStrand[0] == PlusStrand ? task.mSplitAlignSeqStart[0] + best.first - 1
                                                              : task.mSplitAlignSeqStart[0] + task.mSplitAlignSeqLength[0] - best.first;
         breakPos[1] = task.mSplitSeqStrand[1] == PlusStrand ? task.mSplitAlignSeqStart[1] + best.second + 1
