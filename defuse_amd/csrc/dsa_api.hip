@@ -194,6 +194,7 @@ struct dsa_ctx {
     bool have_results = false;
 
     dsa_timing timing{};
+    dsa_kernel_counts kcounts{};     // which kernels swept the last run (dsa_get_kernel_counts)
 };
 
 hipStream_t dsa_ctx::main_stream() const { return lanes->lane[0].stream; }
@@ -547,6 +548,7 @@ int phase2(dsa_ctx* ctx, PipeLane& L)
         const Counters c = L.host->ctr;
         const bool tiers_ok = (c.need_tiers & ~L.tiers_launched) == 0;
         L.tier_hint = tiers_ok ? c.need_tiers : 0xFu;          // what the next slice of this lane launches
+        if (!tiers_ok) ctx->kcounts.slices_rerun += 1;
         if (tiers_ok && c.n_kept <= L.d_kept.cap && c.n_tasks <= L.d_tasks.cap && c.n_masks <= L.d_masks.cap / 2 && c.n_gtasks <= L.d_gtasks.cap) break;
         if (attempt >= 3) return fail(ctx, DSA_E_DEVICE, "finish stage did not converge");
         HIPC(L.d_kept.reserve(c.n_kept + 1024));
@@ -560,6 +562,18 @@ int phase2(dsa_ctx* ctx, PipeLane& L)
     diag_dump_slice(L.d_stats.p, L.d_gtasks.p, (size_t)L.host->ctr.n_gtasks, L.d_tasks.p, (size_t)L.host->ctr.n_tasks);
 #endif
     L.last_gtasks = L.host->ctr.n_gtasks;
+    {
+        // the workgroups as the fill kernels counted them in the attempt that stands (each attempt starts from zero)
+        dsa_kernel_counts& kc = ctx->kcounts;
+        const unsigned* w = L.host->ctr.fill_wgs;
+        for (int t = 0; t < 3; ++t) {
+            kc.fast_wgs[t] += w[FILL_WGS_FAST + 2 * t];
+            kc.fast_wide_wgs[t] += w[FILL_WGS_FAST + 2 * t + 1];
+        }
+        kc.generic_wgs += w[FILL_WGS_GENERIC];
+        kc.workgroups += s.g.n_wgs;
+        kc.slices += 1;
+    }
     ctx->timing.cells += (int64_t)L.host->plan.cells;
     const int64_t n_rec = L.host->n_rec;
     if (!(L.emit_early && (uint64_t)n_rec <= L.emit_cap)) {
@@ -942,6 +956,7 @@ int run_long(dsa_ctx* ctx)
     hipStream_t st = ctx->lanes->lane[0].stream;
     std::vector<LongState>& hs = ctx->h_long_state;
     hs.assign((size_t)nl, LongState{});
+    for (LongState& x : hs) x.max_score = -1;      // k_long_rows writes every pair it sweeps (>= 0): counted below
     int64_t work = 0, rows_max = 0;
     for (int k = 0; k < nl; ++k) {
         const LongDesc& d = ctx->h_long[(size_t)k];
@@ -962,6 +977,7 @@ int run_long(dsa_ctx* ctx)
     int64_t bits = 0;
     for (int k = 0; k < nl; ++k) {
         const LongDesc& d = ctx->h_long[(size_t)k];
+        ctx->kcounts.long_pairs += hs[(size_t)k].max_score >= 0 ? 1 : 0;
         hs[(size_t)k].bits_off = bits;
         bits += (int64_t)hs[(size_t)k].n_kept * (long_bitmap_words(d.ref0_len) + long_bitmap_words(d.ref1_len));
     }
@@ -1024,6 +1040,7 @@ int dsa_run(dsa_ctx* ctx, int64_t* out_n)
     ctx->n_records = 0;
     ctx->have_results = false;
     ctx->timing = dsa_timing{};
+    ctx->kcounts = dsa_kernel_counts{};
     for (const PipeLane& L : ctx->lanes->lane)
         if (L.slice >= 0 || L.emit_pending) {       // left behind by a run that did not end (another context's, on shared lanes)
             reset_lanes(ctx);
@@ -1049,6 +1066,7 @@ int dsa_run(dsa_ctx* ctx, int64_t* out_n)
     // stage times are per-stream sums and overlap between the lanes; total_ms is the elapsed time
     ctx->timing.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ctx->timing.n_records = ctx->n_records;
+    ctx->kcounts.generic_tasks = ctx->timing.n_generic_tasks;
     ctx->have_results = true;
     if (out_n) *out_n = ctx->n_records;
     return DSA_OK;
@@ -1084,6 +1102,13 @@ int dsa_get_timing(const dsa_ctx* ctx, dsa_timing* out)
 {
     if (!ctx || !out) return DSA_E_ARG;
     *out = ctx->timing;
+    return DSA_OK;
+}
+
+int dsa_get_kernel_counts(const dsa_ctx* ctx, dsa_kernel_counts* out)
+{
+    if (!ctx || !out) return DSA_E_ARG;
+    *out = ctx->kcounts;
     return DSA_OK;
 }
 

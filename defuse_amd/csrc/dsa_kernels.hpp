@@ -247,7 +247,12 @@ struct Counters {          // device-side allocation cursors (and overflow detec
     unsigned long long n_kept, n_tasks, n_masks, n_gtasks;
     unsigned need_tiers;   // bit t: some workgroup of the slice belongs to fill kernel t (1, 2: split-table tiers, 3: generic)
     unsigned pad_;
+    // workgroups each fill kernel swept, counted by the kernel itself once it owns the workgroup (dsa_get_kernel_counts):
+    // FILL_WGS_FAST + 2 * TIER + WIDE for k_fill_fast<TIER, WIDE>, FILL_WGS_GENERIC for k_fill_generic
+    unsigned fill_wgs[8];
 };
+constexpr int FILL_WGS_FAST = 0;
+constexpr int FILL_WGS_GENERIC = 6;
 
 __device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
 
@@ -1283,6 +1288,7 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
 {
     __shared__ FinishLds fl;
     if (wg_tier[blockIdx.x] != TIER_GENERIC) return;     // a table kernel owns this workgroup (uniform)
+    if (threadIdx.x == 0) atomicAdd(&fb.ctr->fill_wgs[FILL_WGS_GENERIC], 1u);
     const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WG_WAVES + (threadIdx.x >> 6)));
     if (w < g.n_waves) {                         // whole waves past the end only join the combine barriers
         const int lane = threadIdx.x & 63;
@@ -1597,6 +1603,7 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
         }
         return;
     }
+    if (threadIdx.x == 0) atomicAdd(&fb.ctr->fill_wgs[FILL_WGS_FAST + 2 * TIER + (WIDE ? 1 : 0)], 1u);   // this kernel sweeps the workgroup
     const int nch_wg = s_nch;
 
     const uint32_t* tb = T + my_group * (SPLIT ? TGROUP_SPLIT : TGROUP);
@@ -1881,6 +1888,7 @@ __global__ void k_reset_finish(Counters* ctr, int64_t* rec_count_end)
     if (threadIdx.x == 0) {
         ctr->n_kept = ctr->n_tasks = ctr->n_masks = ctr->n_gtasks = 0;
         ctr->need_tiers = 0;
+        for (int k = 0; k < 8; ++k) ctr->fill_wgs[k] = 0;
         *rec_count_end = 0;
     }
 }

@@ -20,7 +20,7 @@ RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("fusion_id", "frag", "read_end", "
 assert FUSION_DTYPE.itemsize == 20 and PAIR_DTYPE.itemsize == 20 and RECORD_DTYPE.itemsize == 40
 
 EXPORTS = ["dsa_create", "dsa_destroy", "dsa_get_limits", "dsa_last_error", "dsa_version", "dsa_build_flags", "dsa_device_count", "dsa_pick_device", "dsa_pick_device_among", "dsa_set_plan_options", "dsa_set_scratch_budget", "dsa_share_scratch", "dsa_align_batch",
-           "dsa_upload", "dsa_plan", "dsa_run", "dsa_download", "dsa_copy_records_device", "dsa_get_timing", "dsa_set_stream", "dsa_synchronize",
+           "dsa_upload", "dsa_plan", "dsa_run", "dsa_download", "dsa_copy_records_device", "dsa_get_timing", "dsa_get_kernel_counts", "dsa_set_stream", "dsa_synchronize",
            "dsa_stream_create", "dsa_stream_destroy", "dsa_stream_submit", "dsa_stream_collect", "dsa_stream_recollect", "dsa_stream_last_error",
            "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister"]
 
@@ -39,6 +39,13 @@ class Timing(ctypes.Structure):
                 ("total_ms", ctypes.c_float), ("fill_launches", ctypes.c_int32), ("n_generic_tasks", ctypes.c_int32),
                 ("cells", ctypes.c_int64), ("n_records", ctypes.c_int64), ("n_replay_tasks", ctypes.c_int64),
                 ("plan_ms", ctypes.c_float), ("pad_", ctypes.c_float)]
+
+
+class KernelCounts(ctypes.Structure):
+    """dsa_kernel_counts: which kernels swept the last run, as counted on the device."""
+    _fields_ = [("fast_wgs", ctypes.c_int64 * 3), ("fast_wide_wgs", ctypes.c_int64 * 3), ("generic_wgs", ctypes.c_int64),
+                ("workgroups", ctypes.c_int64), ("slices", ctypes.c_int64), ("slices_rerun", ctypes.c_int64),
+                ("long_pairs", ctypes.c_int64), ("generic_tasks", ctypes.c_int64)]
 
 
 class DsaError(RuntimeError):
@@ -74,6 +81,7 @@ def load_library():
         lib.dsa_download.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
         lib.dsa_copy_records_device.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
         lib.dsa_get_timing.argtypes = [vp, ctypes.POINTER(Timing)]
+        lib.dsa_get_kernel_counts.argtypes = [vp, ctypes.POINTER(KernelCounts)]
         lib.dsa_set_stream.argtypes = [vp, vp]
         lib.dsa_synchronize.argtypes = [vp]
         lib.dsa_set_scratch_budget.argtypes = [vp, i64]
@@ -201,6 +209,17 @@ class Context:
         t = Timing()
         self.lib.dsa_get_timing(self.h, ctypes.byref(t))
         return t
+
+    def kernel_counts(self):
+        """dsa_get_kernel_counts of the last run() / align_batch(), as a dict: "fast" and "fast_wide" (workgroups per table
+        tier 0..2 of k_fill_fast, narrow and WIDE instantiation), "generic" (workgroups of k_fill_generic), "workgroups",
+        "slices", "slices_rerun", "long_pairs", "generic_tasks"."""
+        k = KernelCounts()
+        rc = self.lib.dsa_get_kernel_counts(self.h, ctypes.byref(k))
+        if rc != 0:
+            self._err(rc)
+        return dict(fast=list(k.fast_wgs), fast_wide=list(k.fast_wide_wgs), generic=k.generic_wgs, workgroups=k.workgroups,
+                    slices=k.slices, slices_rerun=k.slices_rerun, long_pairs=k.long_pairs, generic_tasks=k.generic_tasks)
 
     def align_batch_into(self, ref_bytes, fusions, read_bytes, pairs, out):
         """dsa_align_batch on the caller's arrays as they are (no copies: pinned buffers stay pinned); the records go to

@@ -98,6 +98,21 @@ typedef struct dsa_timing {
     float   pad_;
 } dsa_timing;
 
+/* Which kernels swept the most recent run of a ctx (dsa_run, dsa_align_batch), as the device counted it: every fill kernel
+ * adds one to its own count for each workgroup it sweeps (the owner k_fill_fast<0> chose for it, after any hand-over of a
+ * workgroup with read bytes outside A/C/G/T/N to the generic kernel).  For tests and measurements: which code path a batch
+ * really took.  Counts of a slice that was run again are those of its last attempt. */
+typedef struct dsa_kernel_counts {
+    int64_t fast_wgs[3];          /* workgroups swept by k_fill_fast<tier>, tier 0 (25-row tables), 1, 2 (split tables)      */
+    int64_t fast_wide_wgs[3];     /* ... by its WIDE instantiation (uploads whose widest window has 9-16 tiles)             */
+    int64_t generic_wgs;          /* workgroups swept by k_fill_generic                                                     */
+    int64_t workgroups;           /* workgroups of all slices (each is swept by exactly one of the above)                   */
+    int64_t slices;
+    int64_t slices_rerun;         /* slices run again because the fill kernel of one of their workgroups was not launched   */
+    int64_t long_pairs;           /* pairs swept by the 32-bit kernels (reads beyond 7600 bases, windows beyond 16320)       */
+    int64_t generic_tasks;        /* tiles re-run by the generic replay kernel (dsa_timing.n_generic_tasks)                  */
+} dsa_kernel_counts;
+
 /* ---- context ---------------------------------------------------------------------------- */
 int  dsa_create(dsa_ctx** out, int device);     /* device = HIP ordinal; fails (DSA_E_DEVICE) without a GPU */
 void dsa_destroy(dsa_ctx* ctx);
@@ -163,6 +178,7 @@ int dsa_download(dsa_ctx* ctx, dsa_record* out, int64_t out_cap, int64_t* out_n)
  * records never visit the host.  This is what the multi-GPU gather sends over RCCL. */
 int dsa_copy_records_device(dsa_ctx* ctx, void* out_device, int64_t out_cap, int64_t* out_n);
 int dsa_get_timing(const dsa_ctx* ctx, dsa_timing* out);
+int dsa_get_kernel_counts(const dsa_ctx* ctx, dsa_kernel_counts* out);
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the ctx's own; pass the
  * hipStream_t as an opaque pointer, NULL restores the private stream. */
 int dsa_set_stream(dsa_ctx* ctx, void* hip_stream);

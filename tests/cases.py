@@ -194,3 +194,138 @@ def edge_batch():
         bb.add_read(f, r0[30:64] + r1[0:30])
         bb.add_read(f, r0[40:64] + r1[100:128])
     return bb.arrays()
+
+
+_COMP = bytes.maketrans(b"ACGTNacgtn", b"TGCANtgcan")
+
+
+def revcomp(s: bytes) -> bytes:
+    return s.translate(_COMP)[::-1]
+
+
+def chunk_genome(rng, length=300_000):
+    """A synthetic genome with what makes windows and reads of the real one awkward: tandem repeats and duplicated segments (tied
+    columns and read splits), soft-masked lowercase stretches and runs of N."""
+    g = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=length)].copy()
+    for _ in range(length // 2000):                           # tandem repeats, units of 1-6 bases over 20-200 bases
+        unit = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=int(rng.integers(1, 7)))]
+        n = int(rng.integers(20, 201))
+        p = int(rng.integers(0, length - n))
+        g[p:p + n] = np.resize(unit, n)
+    for _ in range(length // 5000):                           # duplicated segments of 100-600 bases, 1 % diverged
+        n = int(rng.integers(100, 601))
+        a, b = int(rng.integers(0, length - n)), int(rng.integers(0, length - n))
+        seg = g[a:a + n].copy()
+        mut = rng.random(n) < 0.01
+        seg[mut] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=int(mut.sum()))]
+        g[b:b + n] = seg
+    for _ in range(length // 4000):                           # soft-masked stretches
+        n = int(rng.integers(30, 400))
+        p = int(rng.integers(0, length - n))
+        g[p:p + n] |= 0x20
+    for _ in range(length // 20000):                          # runs of N
+        n = int(rng.integers(5, 120))
+        p = int(rng.integers(0, length - n))
+        g[p:p + n] = ord("N")
+    return g.tobytes()
+
+
+def chunk_batch(seed, n_pairs=100_000, lq=76, ufrag=300, sfrag=30, long_read=False):
+    """Candidates in the shape dosplitalign enumerates them for one chunk of reads (SplitReadRealigner::DoAlignment,
+    tools/SplitAlignment.cpp:266-303): many fusions with 1-7 candidates of their own (and now and then one a neighbouring fusion shares), windows cut from one genome (repeats, duplicated
+    segments, soft-masked lowercase, runs of N) whose lengths follow synth.window_length over region lengths that differ per
+    fusion and per side (windows shorter than the read included), pairs in read-major order (one fusion's candidates are not
+    contiguous, a read is a candidate of several fusions), reads that cross the junction, lie inside one window, align nowhere,
+    and their reverse complements.  long_read: one read of 7700 bases, for the 32-bit kernels.  Deterministic in the arguments."""
+    from defuse_amd import synth
+    rng = np.random.Generator(np.random.PCG64(seed))
+    genome = chunk_genome(rng)
+    G = len(genome)
+    bb = BatchBuilder()
+    max_region = synth.window_length(ufrag, sfrag, lq, lq, 0) + 2 * lq - 8      # longer regions leave windows of fewer than 8 bases
+    wins = []
+    n_fusions = 0
+    cand = []                                  # (read order key, fusion, read bytes, revcomp)
+    while len(cand) < n_pairs:
+        f = n_fusions
+        n_fusions += 1
+        sides = []
+        for _ in range(2):
+            region = int(rng.integers(1, max_region))
+            lr = synth.window_length(ufrag, sfrag, lq, lq, region)
+            p = int(rng.integers(0, G - lr))
+            sides.append(genome[p:p + lr])
+        ref0, ref1 = sides
+        bb.add_fusion(ref0, ref1, fusion_id=3 * f + 1)
+        wins.append((ref0, ref1))
+        for _ in range(int(rng.integers(1, 8))):
+            kind = int(rng.integers(0, 10))
+            if kind < 5:                                       # crosses the junction
+                a = int(rng.integers(4, lq - 3))
+                first = int(rng.integers(0, len(ref0) + 1))
+                s1 = int(rng.integers(0, len(ref1) + 1))
+                read = (ref0[max(0, first - a):first] + ref1[s1:s1 + lq - a])
+            elif kind < 7:                                     # inside one window
+                w = ref0 if kind == 5 else ref1
+                p = int(rng.integers(0, max(1, len(w) - lq + 1)))
+                read = w[p:p + lq]
+            else:                                              # a decoy from elsewhere in the genome
+                p = int(rng.integers(0, G - lq))
+                read = genome[p:p + lq]
+            if len(read) < lq:                                 # a short window: the read goes on in the genome
+                p = int(rng.integers(0, G - lq))
+                read = read + genome[p:p + lq - len(read)]
+            read = read.upper()
+            rc = int(rng.integers(0, 2))
+            if rc:
+                read = revcomp(read)
+            cand.append((int(rng.integers(0, 1 << 30)), f, read, rc))
+            if rng.random() < 0.15 and f > 0:                  # the same read is a candidate of a neighbouring fusion too
+                cand.append((cand[-1][0], f - 1, read, rc))
+    cand = cand[:n_pairs]
+    order = sorted(range(len(cand)), key=lambda k: (cand[k][0], cand[k][1]))    # read-major
+    reads = bytearray()
+    offs = np.zeros(len(cand), dtype=np.int64)
+    for j, k in enumerate(order):
+        offs[j] = len(reads)
+        reads += cand[k][2]
+    buf = np.frombuffer(bytes(reads), dtype=np.uint8).copy()
+    sub = rng.random(buf.size) < 0.01                          # sequencing errors, an N now and then
+    buf[sub] = np.frombuffer(b"ACGTN", dtype=np.uint8)[rng.choice(5, size=int(sub.sum()), p=[0.24, 0.24, 0.24, 0.24, 0.04])]
+    if long_read:
+        ref0, ref1 = wins[0]
+        lr = 7700
+        long = np.frombuffer((ref0 * (lr // max(1, len(ref0)) + 1))[:lr // 2] + (ref1 * (lr // max(1, len(ref1)) + 1))[:lr - lr // 2],
+                             dtype=np.uint8)
+        offs = np.append(offs, buf.size)
+        buf = np.concatenate([buf, long])
+    fusions = np.array(bb.fusions, dtype=FUSION_DTYPE)
+    n = len(offs)
+    pairs = np.zeros(n, dtype=PAIR_DTYPE)
+    pairs["fusion_idx"][:len(order)] = [cand[k][1] for k in order]
+    pairs["revcomp"][:len(order)] = [cand[k][3] for k in order]
+    pairs["read_off"] = offs
+    pairs["read_len"][:len(order)] = [len(cand[k][2]) for k in order]
+    pairs["frag"][:len(order)] = [cand[k][0] >> 1 for k in order]
+    pairs["read_end"][:len(order)] = [cand[k][0] & 1 for k in order]
+    if long_read:                                             # among the first pairs, so that the first slice holds it
+        pairs[-1] = (0, offs[-1], buf.size - offs[-1], 5, 0, 0, (0, 0))
+        pairs = np.concatenate([pairs[:100], pairs[-1:], pairs[100:-1]])
+    ref = np.frombuffer(bytes(bb.ref), dtype=np.uint8).copy()
+    return ref, fusions, buf, pairs
+
+
+def group_by_fusion(batch, exp):
+    """The batch with its pairs stably sorted by fusion (the order dosplitalign hands them to the aligner in), and the oracle
+    records `exp` of the original order rewritten for it (records follow their pairs; pair_idx renumbered)."""
+    ref, fus, reads, pairs = batch
+    perm = np.argsort(pairs["fusion_idx"], kind="stable")
+    n = len(pairs)
+    counts = np.bincount(exp["pair_idx"], minlength=n)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    c2 = counts[perm]
+    first2 = np.concatenate([[0], np.cumsum(c2)[:-1]])
+    idx = np.repeat(starts[perm] - first2, c2) + np.arange(int(c2.sum()))
+    exp2 = exp[idx].copy()
+    exp2["pair_idx"] = np.repeat(np.arange(n, dtype=np.int32), c2)
+    return (ref, fus, reads, pairs[perm].copy()), exp2

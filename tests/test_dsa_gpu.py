@@ -67,6 +67,8 @@ def test_parity_single_fusion_fast_path(gpu_ctx, ora):
         bb.add_read(f, read)
     got = check_batch(gpu_ctx, ora, bb.arrays())
     assert len(got) > 300
+    kc = gpu_ctx.kernel_counts()
+    assert kc["fast"][0] == kc["workgroups"] == 3, kc
 
 
 @pytest.mark.parametrize("lq,lr,n_reads", [(7600, 9000, 1), (300, 16320, 2), (1000, 3000, 4), (5, 40, 8), (8, 64, 8), (9, 65, 8)])
@@ -122,6 +124,7 @@ def test_parity_beyond_the_16_bit_kernels(built, ora):
     assert all(np.any(exp["pair_idx"] == p) for p in long_pairs)          # every long pair really aligns
     assert np.sum(exp["pair_idx"] == 61) >= 2                             # the repeated segment: tied columns
     assert ctx.timing().cells > 2 * 10001 * 12001
+    assert ctx.kernel_counts()["long_pairs"] == len(long_pairs)
     ctx.close()
     os.environ["DEFUSE_DSA_SLICE_PAIRS"] = "256"                          # two slices, long pairs in the first
     try:
@@ -183,7 +186,8 @@ def test_parity_sweep_plans(gpu_ctx, ora, monkeypatch):
 
 def test_parity_split_table_tier(gpu_ctx, ora):
     """Workgroups of five to ten fusions (30 reads each, reads over {A,C,G,T,N}) take the fill kernel with two
-    small LDS tables per fusion; twelve reads per fusion push workgroups past ten fusions onto the generic one."""
+    small LDS tables per fusion; twelve reads per fusion push workgroups past twenty fusions onto its second tier (twice the
+    LDS per workgroup)."""
     import numpy as np
     rng = np.random.default_rng(79)
     for reads_per_fusion, n_fusions in ((30, 40), (12, 60)):
@@ -200,6 +204,12 @@ def test_parity_split_table_tier(gpu_ctx, ora):
                 bb.add_read(f, read)
         got = check_batch(gpu_ctx, ora, bb.arrays())
         assert len(got) > 200
+        kc = gpu_ctx.kernel_counts()
+        assert sum(kc["fast"]) + kc["generic"] == kc["workgroups"] and sum(kc["fast_wide"]) == 0, kc
+        if reads_per_fusion == 30:          # eight or nine fusions per workgroup
+            assert kc["fast"][1] > 0 and kc["fast"][1] + kc["fast"][2] + kc["generic"] == kc["workgroups"], kc
+        else:                               # 21-22 fusions of twelve reads: the second split-table tier (the last, short one: the first)
+            assert kc["fast"][0] == kc["generic"] == 0 and kc["fast"][1] <= 1 and kc["fast"][2] > 0, kc
 
 
 def test_parity_exotic_reads_hand_workgroups_over(gpu_ctx, ora):
@@ -218,6 +228,8 @@ def test_parity_exotic_reads_hand_workgroups_over(gpu_ctx, ora):
             bb.add_read(f, read)
     got = check_batch(gpu_ctx, ora, bb.arrays())
     assert len(got) > 800
+    kc = gpu_ctx.kernel_counts()          # six lowercase reads in at most six of the eight workgroups, the others on tier 0
+    assert 1 <= kc["generic"] <= 6 and kc["fast"] == [kc["workgroups"] - kc["generic"], 0, 0] and kc["workgroups"] == 8, kc
 
 
 def test_parity_ties(gpu_ctx, ora):
@@ -346,12 +358,16 @@ def test_plan_again_and_kernels_a_lane_did_not_expect(built, ora):
     ctx.run()
     assert ctx.download().tobytes() == exp_big.tobytes()
     assert ctx.timing().plan_ms > 0
+    assert ctx.kernel_counts()["slices_rerun"] == 0
     ctx.upload(*small)
     ctx.run()
     assert ctx.download().tobytes() == exp_small.tobytes()
+    kc = ctx.kernel_counts()
+    assert kc["slices_rerun"] == 1 and kc["fast"][1] > 0 and kc["fast"][2] + kc["generic"] > 0, kc
     ctx.plan()
     ctx.run()
     assert ctx.download().tobytes() == exp_small.tobytes()
+    assert ctx.kernel_counts()["slices_rerun"] == 0
     ctx.upload(*big)
     ctx.run()
     assert ctx.download().tobytes() == exp_big.tobytes()
@@ -430,6 +446,8 @@ def test_many_fusions_with_few_reads_equal_the_oracle(built, shape):
     got = ctx.align_batch(*batch)
     assert len(got) == len(exp) and got.tobytes() == exp.tobytes(), shape
     assert ctx.timing().n_generic_tasks > 0
+    kc = ctx.kernel_counts()
+    assert kc["generic"] > 0 and sum(kc["fast"]) + sum(kc["fast_wide"]) + kc["generic"] == kc["workgroups"], kc
     ctx.close()
 
 

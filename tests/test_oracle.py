@@ -113,6 +113,40 @@ def test_struct_layouts_match_header(built):
     from defuse_amd import dsa
     assert dsa.FUSION_DTYPE.itemsize == 20 and dsa.PAIR_DTYPE.itemsize == 20 and dsa.RECORD_DTYPE.itemsize == 40
     assert ctypes.sizeof(dsa.Timing) == 56 and ctypes.sizeof(dsa.Limits) == 12      # dsa_timing grew by plan_ms + pad_
+    # dsa_kernel_counts: the binding's fields in the header's order, twelve 64-bit words
+    import re
+    header = open(os.path.join(ROOT, "include", "defuse_dsa.h")).read()
+    body = re.search(r"typedef struct dsa_kernel_counts \{(.*?)\} dsa_kernel_counts;", header, re.S).group(1)
+    fields = re.findall(r"int64_t\s+(\w+)(?:\[(\d+)\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert [(n, int(k or 1)) for n, k in fields] == [(n, getattr(t, "_length_", 1)) for n, t in dsa.KernelCounts._fields_]
+    assert ctypes.sizeof(dsa.KernelCounts) == 96
+
+
+def test_chunk_batch_is_deterministic_and_chunk_shaped(ora):
+    """The generator of the chunk-shaped parity cases (tests/test_dsa_tiers.py): the same bytes for a seed, and the features
+    the cases rely on (per-fusion and per-side windows, some shorter than the read, soft-masked and N bases in the windows,
+    uppercase reads over A/C/G/T/N, reverse complements, fusions whose candidates are not contiguous)."""
+    import hashlib
+    b = cases.chunk_batch(3, n_pairs=3000, lq=100)
+    h = hashlib.sha256()
+    for a in b:
+        h.update(a.tobytes())
+    assert h.hexdigest()[:16] == "6fcd482b0cb018e4"
+    ref, fus, reads, pairs = b
+    assert len(pairs) == 3000 and len(fus) > 400
+    assert (np.minimum(fus["ref0_len"], fus["ref1_len"]) < 100).any() and (fus["ref0_len"] != fus["ref1_len"]).mean() > 0.5
+    assert fus["ref0_len"].max() == 390 and fus["ref0_len"].min() >= 8
+    assert (ref >= ord("a")).sum() > 1000 and (ref == ord("N")).sum() > 100
+    assert set(np.unique(reads).tolist()) == set(b"ACGTN")
+    assert 0.4 < pairs["revcomp"].mean() < 0.6
+    f = pairs["fusion_idx"]
+    runs = 1 + int((f[1:] != f[:-1]).sum())
+    assert runs > 0.9 * len(pairs)                              # read-major: a fusion's candidates are scattered
+    # the records of the pairs grouped by fusion (how the chunk cases run the planned sweep) are the oracle's own for that order
+    small = cases.chunk_batch(4, n_pairs=400, lq=76)
+    grouped, exp = cases.group_by_fusion(small, ora.align_batch(*small))
+    assert (np.diff(grouped[3]["fusion_idx"]) >= 0).all() and len(exp) > 100
+    assert exp.tobytes() == ora.align_batch(*grouped).tobytes()
 
 
 def test_oracle_batch_matches_python_loop(ora):
