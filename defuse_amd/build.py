@@ -119,7 +119,7 @@ def compile_lib(out, extra_flags=()):
     return out
 
 
-TOOLS = ["dosplitalign", "evalsplitalign", "setcover", "clustermatepairs", "localalign", "defuse_glue", "calccov"]
+TOOLS = ["dosplitalign", "evalsplitalign", "setcover", "clustermatepairs", "localalign", "defuse_glue", "calccov", "matealign"]
 
 
 def build_tools(force=False):

@@ -18,6 +18,10 @@
 //
 // Pairs are sorted by (sequence length, reference length) so that the lanes of a wave sweep about the
 // same number of rows and tiles.
+//
+// Two ways in: la_align_batch_min takes references and sequences from one host pool (k_pack fills the codes);
+// la_align_windows_min (matealign) cuts every reference out of a genome kept in HBM by la_genome_create, from a
+// 40-byte descriptor per pair (k_pack_win).  Both run the same launch groups and the same two kernels.
 #include <hip/hip_runtime.h>
 
 #include "hip_raii.hpp"
@@ -25,6 +29,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <numeric>
@@ -101,6 +106,60 @@ __global__ void k_pack(const uint8_t* __restrict__ pool, const la_item* __restri
         uint32_t code = 0;
 #pragma unroll
         for (int f = 0; f < ITEMS; ++f) code |= ((ref[f] != nullptr && i < ln.lr[f]) ? (uint32_t)ref[f][i] : REF_PAD) << (16 * f);
+        refcodes[wv.ref_off + (int64_t)i * WAVE + lane] = code;
+    }
+    for (int j = threadIdx.x >> 6; j < wv.rows4; j += blockDim.x >> 6) {
+        uint32_t code = 0;
+#pragma unroll
+        for (int f = 0; f < ITEMS; ++f)
+            code |= ((seq[f] != nullptr && j >= 1 && j <= ln.ls[f]) ? (uint32_t)seq[f][j - 1] : ROW_PAD) << (16 * f);
+        rowcodes[wv.row_off + rowidx(j, lane)] = code;
+    }
+}
+
+__device__ __forceinline__ uint32_t complement(uint32_t b)     // tools/Common.cpp:32-54: ACGTacgt only
+{
+    const uint32_t up = b & ~0x20u;
+    const uint32_t c = up == 'A' ? 'T' : up == 'T' ? 'A' : up == 'C' ? 'G' : up == 'G' ? 'C' : 0u;
+    return c ? (c | (b & 0x20u)) : b;
+}
+
+// k_pack for windows cut from a genome in HBM (la_align_windows_min): the reference of a pair is
+// 'N' x pad_left + genome[slice_off, + slice_len) + 'N' x pad_right, reversed and complemented when revcomp is set
+template <int ITEMS>
+__global__ void k_pack_win(const uint8_t* __restrict__ genome, const uint8_t* __restrict__ pool, const la_window* __restrict__ wins,
+                           const Lane* __restrict__ lanes, const Wave* __restrict__ waves, uint32_t* __restrict__ refcodes,
+                           uint32_t* __restrict__ rowcodes)
+{
+    const int w = blockIdx.x;
+    const Wave wv = waves[w];
+    const int lane = threadIdx.x & 63;
+    const Lane ln = lanes[(int64_t)w * WAVE + lane];
+    const uint8_t* slice[2] = {nullptr, nullptr};
+    const uint8_t* seq[2] = {nullptr, nullptr};
+    int32_t pl[2] = {0, 0}, sl[2] = {0, 0}, rc[2] = {0, 0};
+#pragma unroll
+    for (int f = 0; f < ITEMS; ++f)
+        if (ln.out[f] >= 0) {
+            const la_window wd = wins[ln.out[f]];
+            slice[f] = genome + wd.slice_off;
+            seq[f] = pool + wd.seq_off;
+            pl[f] = wd.pad_left;
+            sl[f] = wd.slice_len;
+            rc[f] = wd.revcomp;
+        }
+    for (int i = threadIdx.x >> 6; i < wv.nch * W; i += blockDim.x >> 6) {
+        uint32_t code = 0;
+#pragma unroll
+        for (int f = 0; f < ITEMS; ++f) {
+            uint32_t c = REF_PAD;
+            if (slice[f] != nullptr && i < ln.lr[f]) {
+                const int q = (rc[f] ? ln.lr[f] - 1 - i : i) - pl[f];          // byte of the window before reversal
+                c = (q >= 0 && q < sl[f]) ? (uint32_t)slice[f][q] : (uint32_t)'N';
+                if (rc[f]) c = complement(c);
+            }
+            code |= c << (16 * f);
+        }
         refcodes[wv.ref_off + (int64_t)i * WAVE + lane] = code;
     }
     for (int j = threadIdx.x >> 6; j < wv.rows4; j += blockDim.x >> 6) {
@@ -284,6 +343,12 @@ __global__ __launch_bounds__(WG_WAVES * WAVE) void k_la32(const Lane* __restrict
 
 }  // namespace la
 
+struct la_genome {             // include/defuse_la.h: the contig bytes of a genome in HBM
+    int device;
+    uint8_t* bytes;
+    int64_t len;
+};
+
 namespace {
 
 using namespace la;
@@ -319,7 +384,11 @@ struct Group {
     int64_t ref_dwords = 0, row_dwords = 0, bnd_dwords = 0;
 };
 
-void add_wave(Group& g, const la_item* items, const int32_t* min_score, const int64_t* order, int64_t n, int items_per_lane)
+inline int32_t ref_len(const la_item& it) { return it.ref_len; }
+inline int32_t ref_len(const la_window& wd) { return wd.pad_left + wd.slice_len + wd.pad_right; }
+
+template <class Item>
+void add_wave(Group& g, const Item* items, const int32_t* min_score, const int64_t* order, int64_t n, int items_per_lane)
 {
     Wave wv{};
     wv.ref_off = g.ref_dwords;
@@ -333,12 +402,12 @@ void add_wave(Group& g, const la_item* items, const int32_t* min_score, const in
             ln.need[f] = NO_NEED;
             const int64_t k = (int64_t)lane * items_per_lane + f;
             if (f < items_per_lane && k < n) {
-                const la_item& it = items[order[k]];
+                const Item& it = items[order[k]];
                 ln.out[f] = (int32_t)order[k];
-                ln.lr[f] = it.ref_len;
+                ln.lr[f] = ref_len(it);
                 ln.ls[f] = it.seq_len;
                 if (min_score) ln.need[f] = std::max(min_score[order[k]], NO_NEED);
-                lr_max = std::max(lr_max, it.ref_len);
+                lr_max = std::max(lr_max, ln.lr[f]);
                 ls_max = std::max(ls_max, it.seq_len);
             }
         }
@@ -351,6 +420,110 @@ void add_wave(Group& g, const la_item* items, const int32_t* min_score, const in
     g.row_dwords += (int64_t)wv.rows4 * WAVE;
     g.bnd_dwords += 2 * (int64_t)wv.rows4 * WAVE;
     g.waves.push_back(wv);
+}
+
+// Everything after the checks of the entry points: the 16-bit / int32 split, launch groups within the scratch budget, and per
+// group the pack step, then k_la16 or k_la32.  The items (la_item or la_window) and the pool go to the device as given;
+// pack(items_per_lane, n_waves, d_pool, d_items, d_lanes, d_waves, d_ref, d_row) launches the step that fills a group's codes.
+template <class Item, class Pack>
+int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const uint8_t* pool, int64_t pool_len, const Item* items,
+                int64_t n_items, const int32_t* min_score, int32_t* scores, la_timing& tm, Pack pack)
+{
+    if (n_items == 0) return DSA_OK;
+    HIPL(hipSetDevice(device));
+
+    // Moves by mismatch are never better than two gaps when mismatch < 2*gap (same for match): clamping
+    // gives the same matrix and keeps the packed kernel's diagonal term non-negative.
+    Params prm{};
+    prm.match = match;
+    prm.mismatch = mismatch;
+    prm.gap = gap;
+    prm.gd = -gap;
+    prm.dm = std::max(match, 2 * gap) - gap;
+    prm.dx = std::max(mismatch, 2 * gap) - gap;
+    prm.mp = std::max(match, 0);
+
+    // longest sequences first; a wave takes consecutive pairs
+    std::vector<int64_t> order((size_t)n_items);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        if (items[a].seq_len != items[b].seq_len) return items[a].seq_len > items[b].seq_len;
+        if (ref_len(items[a]) != ref_len(items[b])) return ref_len(items[a]) > ref_len(items[b]);
+        return a < b;
+    });
+    // the packed kernel takes the pairs whose values fit 16-bit fields
+    const bool scores16 = gap <= 0 && mismatch <= 0 && prm.gd <= 1000 && prm.dm >= 0 && prm.dm <= 1000 && prm.dx >= 0 && prm.dx <= 1000;
+    const int64_t step = std::max(prm.dm, std::max(prm.dx, 1));
+    int64_t first16 = n_items;      // order[first16..) go to the packed kernel (sequence lengths descend)
+    if (scores16) {
+        first16 = 0;
+        while (first16 < n_items && (int64_t)BIAS16 + (int64_t)items[order[first16]].seq_len * step > Y_LIMIT) ++first16;
+    }
+    tm.n_int32 = (int32_t)first16;
+    tm.n_packed16 = (int32_t)(n_items - first16);
+
+    Buf<uint8_t> d_pool;
+    Buf<Item> d_items;
+    Buf<int32_t> d_scores;
+    HIPL(d_pool.alloc((size_t)pool_len));
+    HIPL(d_items.alloc((size_t)n_items));
+    HIPL(d_scores.alloc((size_t)n_items));
+    if (pool_len > 0) HIPL(hipMemcpy(d_pool.p, pool, (size_t)pool_len, hipMemcpyHostToDevice));
+    HIPL(hipMemcpy(d_items.p, items, (size_t)n_items * sizeof(Item), hipMemcpyHostToDevice));
+    hipraii::Event ev[3];                 // destroyed on every return
+    for (auto& e : ev) HIPL(e.create());
+
+    size_t budget_dwords = (size_t)2 << 28;       // 2 GiB of planes per launch group
+    if (const char* e = getenv("DEFUSE_LA_SCRATCH_MB")) budget_dwords = std::max<size_t>(1, (size_t)atoll(e)) << 18;
+
+    auto run_range = [&](int64_t begin, int64_t end, int items_per_lane) -> int {
+        const int64_t per_wave = (int64_t)WAVE * items_per_lane;
+        int64_t k = begin;
+        while (k < end) {
+            Group g;
+            while (k < end) {
+                const int64_t n = std::min(per_wave, end - k);
+                add_wave(g, items, min_score, order.data() + k, n, items_per_lane);
+                k += n;
+                if ((size_t)(g.ref_dwords + g.row_dwords + g.bnd_dwords) >= budget_dwords) break;
+            }
+            Buf<Lane> d_lanes;
+            Buf<Wave> d_waves;
+            Buf<uint32_t> d_ref, d_row, d_bnd;
+            HIPL(d_lanes.alloc(g.lanes.size()));
+            HIPL(d_waves.alloc(g.waves.size()));
+            HIPL(d_ref.alloc((size_t)g.ref_dwords));
+            HIPL(d_row.alloc((size_t)g.row_dwords));
+            HIPL(d_bnd.alloc((size_t)g.bnd_dwords));
+            HIPL(hipMemcpy(d_lanes.p, g.lanes.data(), g.lanes.size() * sizeof(Lane), hipMemcpyHostToDevice));
+            HIPL(hipMemcpy(d_waves.p, g.waves.data(), g.waves.size() * sizeof(Wave), hipMemcpyHostToDevice));
+            const int n_waves = (int)g.waves.size();
+            HIPL(hipEventRecord(ev[0], nullptr));
+            pack(items_per_lane, n_waves, d_pool.p, d_items.p, d_lanes.p, d_waves.p, d_ref.p, d_row.p);
+            HIPL(hipEventRecord(ev[1], nullptr));
+            const unsigned grid = (unsigned)((n_waves + WG_WAVES - 1) / WG_WAVES);
+            if (items_per_lane == 2)
+                hipLaunchKernelGGL(k_la16, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
+                                   d_bnd.p, prm, d_scores.p);
+            else
+                hipLaunchKernelGGL(k_la32, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
+                                   d_bnd.p, prm, d_scores.p);
+            HIPL(hipEventRecord(ev[2], nullptr));
+            HIPL(hipEventSynchronize(ev[2]));
+            HIPL(hipGetLastError());
+            float ms = 0;
+            HIPL(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            tm.pack_ms += ms;
+            HIPL(hipEventElapsedTime(&ms, ev[1], ev[2]));
+            tm.kernel_ms += ms;
+        }
+        return DSA_OK;
+    };
+    int rc = run_range(0, first16, 1);
+    if (rc == DSA_OK) rc = run_range(first16, n_items, 2);
+    if (rc != DSA_OK) return rc;
+    HIPL(hipMemcpy(scores, d_scores.p, (size_t)n_items * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return DSA_OK;
 }
 
 }  // namespace
@@ -383,102 +556,75 @@ int la_align_batch_min(int device, int32_t match, int32_t mismatch, int32_t gap,
         if (timing) *timing = tm;
         return DSA_OK;
     }
-    HIPL(hipSetDevice(device));
-
-    // Moves by mismatch are never better than two gaps when mismatch < 2*gap (same for match): clamping
-    // gives the same matrix and keeps the packed kernel's diagonal term non-negative.
-    Params prm{};
-    prm.match = match;
-    prm.mismatch = mismatch;
-    prm.gap = gap;
-    prm.gd = -gap;
-    prm.dm = std::max(match, 2 * gap) - gap;
-    prm.dx = std::max(mismatch, 2 * gap) - gap;
-    prm.mp = std::max(match, 0);
-
-    // longest sequences first; a wave takes consecutive pairs
-    std::vector<int64_t> order((size_t)n_items);
-    std::iota(order.begin(), order.end(), (int64_t)0);
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        if (items[a].seq_len != items[b].seq_len) return items[a].seq_len > items[b].seq_len;
-        if (items[a].ref_len != items[b].ref_len) return items[a].ref_len > items[b].ref_len;
-        return a < b;
-    });
-    // the packed kernel takes the pairs whose values fit 16-bit fields
-    const bool scores16 = gap <= 0 && mismatch <= 0 && prm.gd <= 1000 && prm.dm >= 0 && prm.dm <= 1000 && prm.dx >= 0 && prm.dx <= 1000;
-    const int64_t step = std::max(prm.dm, std::max(prm.dx, 1));
-    int64_t first16 = n_items;      // order[first16..) go to the packed kernel (sequence lengths descend)
-    if (scores16) {
-        first16 = 0;
-        while (first16 < n_items && (int64_t)BIAS16 + (int64_t)items[order[first16]].seq_len * step > Y_LIMIT) ++first16;
-    }
-    tm.n_int32 = (int32_t)first16;
-    tm.n_packed16 = (int32_t)(n_items - first16);
-
-    Buf<uint8_t> d_pool;
-    Buf<la_item> d_items;
-    Buf<int32_t> d_scores;
-    HIPL(d_pool.alloc((size_t)pool_len));
-    HIPL(d_items.alloc((size_t)n_items));
-    HIPL(d_scores.alloc((size_t)n_items));
-    HIPL(hipMemcpy(d_pool.p, pool, (size_t)pool_len, hipMemcpyHostToDevice));
-    HIPL(hipMemcpy(d_items.p, items, (size_t)n_items * sizeof(la_item), hipMemcpyHostToDevice));
-    hipraii::Event ev[3];                 // destroyed on every return
-    for (auto& e : ev) HIPL(e.create());
-
-    size_t budget_dwords = (size_t)2 << 28;       // 2 GiB of planes per launch group
-    if (const char* e = getenv("DEFUSE_LA_SCRATCH_MB")) budget_dwords = std::max<size_t>(1, (size_t)atoll(e)) << 18;
-
-    auto run_range = [&](int64_t begin, int64_t end, int items_per_lane) -> int {
-        const int64_t per_wave = (int64_t)WAVE * items_per_lane;
-        int64_t k = begin;
-        while (k < end) {
-            Group g;
-            while (k < end) {
-                const int64_t n = std::min(per_wave, end - k);
-                add_wave(g, items, min_score, order.data() + k, n, items_per_lane);
-                k += n;
-                if ((size_t)(g.ref_dwords + g.row_dwords + g.bnd_dwords) >= budget_dwords) break;
-            }
-            Buf<Lane> d_lanes;
-            Buf<Wave> d_waves;
-            Buf<uint32_t> d_ref, d_row, d_bnd;
-            HIPL(d_lanes.alloc(g.lanes.size()));
-            HIPL(d_waves.alloc(g.waves.size()));
-            HIPL(d_ref.alloc((size_t)g.ref_dwords));
-            HIPL(d_row.alloc((size_t)g.row_dwords));
-            HIPL(d_bnd.alloc((size_t)g.bnd_dwords));
-            HIPL(hipMemcpy(d_lanes.p, g.lanes.data(), g.lanes.size() * sizeof(Lane), hipMemcpyHostToDevice));
-            HIPL(hipMemcpy(d_waves.p, g.waves.data(), g.waves.size() * sizeof(Wave), hipMemcpyHostToDevice));
-            const int n_waves = (int)g.waves.size();
-            HIPL(hipEventRecord(ev[0], nullptr));
-            if (items_per_lane == 2)
-                hipLaunchKernelGGL(k_pack<2>, dim3(n_waves), dim3(256), 0, nullptr, d_pool.p, d_items.p, d_lanes.p, d_waves.p, d_ref.p, d_row.p);
-            else
-                hipLaunchKernelGGL(k_pack<1>, dim3(n_waves), dim3(256), 0, nullptr, d_pool.p, d_items.p, d_lanes.p, d_waves.p, d_ref.p, d_row.p);
-            HIPL(hipEventRecord(ev[1], nullptr));
-            const unsigned grid = (unsigned)((n_waves + WG_WAVES - 1) / WG_WAVES);
-            if (items_per_lane == 2)
-                hipLaunchKernelGGL(k_la16, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
-                                   d_bnd.p, prm, d_scores.p);
-            else
-                hipLaunchKernelGGL(k_la32, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
-                                   d_bnd.p, prm, d_scores.p);
-            HIPL(hipEventRecord(ev[2], nullptr));
-            HIPL(hipEventSynchronize(ev[2]));
-            HIPL(hipGetLastError());
-            float ms = 0;
-            HIPL(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            tm.pack_ms += ms;
-            HIPL(hipEventElapsedTime(&ms, ev[1], ev[2]));
-            tm.kernel_ms += ms;
-        }
-        return DSA_OK;
-    };
-    int rc = run_range(0, first16, 1);
-    if (rc == DSA_OK) rc = run_range(first16, n_items, 2);
+    const int rc = align_items(device, match, mismatch, gap, pool, pool_len, items, n_items, min_score, scores, tm,
+                               [](int items_per_lane, int n_waves, const uint8_t* d_pool, const la_item* d_items, const Lane* d_lanes,
+                                  const Wave* d_waves, uint32_t* d_ref, uint32_t* d_row) {
+                                   if (items_per_lane == 2)
+                                       hipLaunchKernelGGL(k_pack<2>, dim3(n_waves), dim3(256), 0, nullptr, d_pool, d_items, d_lanes, d_waves, d_ref, d_row);
+                                   else
+                                       hipLaunchKernelGGL(k_pack<1>, dim3(n_waves), dim3(256), 0, nullptr, d_pool, d_items, d_lanes, d_waves, d_ref, d_row);
+                               });
     if (rc != DSA_OK) return rc;
-    HIPL(hipMemcpy(scores, d_scores.p, (size_t)n_items * sizeof(int32_t), hipMemcpyDeviceToHost));
+    tm.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (timing) *timing = tm;
+    return DSA_OK;
+}
+
+int la_genome_create(int device, const uint8_t* bytes, int64_t len, la_genome** out)
+{
+    if (!out || len < 0 || (len > 0 && !bytes)) return fail(DSA_E_ARG, "null argument");
+    *out = nullptr;
+    HIPL(hipSetDevice(device));
+    uint8_t* d = nullptr;
+    HIPL(hipMalloc((void**)&d, (size_t)std::max<int64_t>(len, 1)));
+    if (len > 0) {
+        const hipError_t e = hipMemcpy(d, bytes, (size_t)len, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return fail(DSA_E_DEVICE, "hipMemcpy of the genome: %s", hipGetErrorString(e));
+        }
+    }
+    *out = new la_genome{device, d, len};
+    return DSA_OK;
+}
+
+void la_genome_destroy(la_genome* genome)
+{
+    if (!genome) return;
+    (void)hipSetDevice(genome->device);
+    (void)hipFree(genome->bytes);
+    delete genome;
+}
+
+int la_align_windows_min(const la_genome* genome, int32_t match, int32_t mismatch, int32_t gap, const uint8_t* pool, int64_t pool_len,
+                         const la_window* windows, int64_t n_windows, const int32_t* min_score, int32_t* scores, la_timing* timing)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    la_timing tm{};
+    if (!genome || n_windows < 0 || (n_windows > 0 && (!windows || !scores || (!pool && pool_len > 0)))) return fail(DSA_E_ARG, "null argument");
+    if (n_windows >= (int64_t)1 << 31) return fail(DSA_E_LIMIT, "more than 2^31-1 pairs");
+    for (int64_t k = 0; k < n_windows; ++k) {
+        const la_window& wd = windows[k];
+        const int64_t lr = (int64_t)wd.pad_left + wd.slice_len + wd.pad_right;
+        if (wd.slice_off < 0 || wd.slice_len < 0 || wd.pad_left < 0 || wd.pad_right < 0 || wd.slice_off + wd.slice_len > genome->len ||
+            lr > INT32_MAX)
+            return fail(DSA_E_ARG, "window %lld lies outside the genome", (long long)k);
+        if (wd.seq_len < 0 || wd.seq_off < 0 || wd.seq_off + wd.seq_len > pool_len)
+            return fail(DSA_E_ARG, "sequence %lld lies outside the pool", (long long)k);
+        tm.cells += (lr + 1) * ((int64_t)wd.seq_len + 1);
+    }
+    const uint8_t* d_genome = genome->bytes;
+    const int rc = align_items(genome->device, match, mismatch, gap, pool, pool_len, windows, n_windows, min_score, scores, tm,
+                               [d_genome](int items_per_lane, int n_waves, const uint8_t* d_pool, const la_window* d_wins, const Lane* d_lanes,
+                                          const Wave* d_waves, uint32_t* d_ref, uint32_t* d_row) {
+                                   if (items_per_lane == 2)
+                                       hipLaunchKernelGGL(k_pack_win<2>, dim3(n_waves), dim3(256), 0, nullptr, d_genome, d_pool, d_wins, d_lanes,
+                                                          d_waves, d_ref, d_row);
+                                   else
+                                       hipLaunchKernelGGL(k_pack_win<1>, dim3(n_waves), dim3(256), 0, nullptr, d_genome, d_pool, d_wins, d_lanes,
+                                                          d_waves, d_ref, d_row);
+                               });
+    if (rc != DSA_OK) return rc;
     tm.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     if (timing) *timing = tm;
     return DSA_OK;

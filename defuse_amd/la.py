@@ -37,3 +37,83 @@ def align_batch(pairs, match, mismatch, gap, device=0, min_score=None):
     if rc != 0:
         raise RuntimeError("la_align_batch_min failed (%d): %s" % (rc, lib.la_last_error().decode()))
     return scores, t
+
+
+LA_WINDOW = np.dtype([("slice_off", np.int64), ("seq_off", np.int64), ("slice_len", np.int32), ("pad_left", np.int32),
+                      ("pad_right", np.int32), ("seq_len", np.int32), ("revcomp", np.int32), ("pad_", np.int32)])
+
+
+def _bind_windows(lib):
+    lib.la_genome_create.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
+    lib.la_genome_destroy.argtypes = [ctypes.c_void_p]
+    lib.la_genome_destroy.restype = None
+    lib.la_align_windows_min.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(LaTiming)]
+    lib.la_last_error.restype = ctypes.c_char_p
+    return lib
+
+
+class Genome:
+    """Contig bytes in HBM (la_genome_create); close() or a with-block frees them."""
+
+    def __init__(self, data, device=0):
+        self._lib = _bind_windows(load_library())
+        buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+        self.len = len(buf) - 1
+        self.handle = ctypes.c_void_p()
+        rc = self._lib.la_genome_create(device, buf.ctypes.data, self.len, ctypes.byref(self.handle))
+        if rc != 0:
+            raise RuntimeError("la_genome_create failed (%d): %s" % (rc, self._lib.la_last_error().decode()))
+
+    def close(self):
+        if self.handle:
+            self._lib.la_genome_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def genome(data, device=0):
+    """The bytes of a genome (contigs concatenated) on the device."""
+    return Genome(data, device)
+
+
+def align_windows(gen, reads, windows, match, mismatch, gap, min_score=None):
+    """la_align_windows_min.  reads: list of byte strings; windows: one (read index, slice_off, slice_len, pad_left,
+    pad_right, revcomp) per pair, or an LA_WINDOW array whose seq_off / seq_len index the concatenated reads.
+    Returns (int32 scores, timing)."""
+    lib = gen._lib
+    pool = b"".join(bytes(r) for r in reads)
+    if isinstance(windows, np.ndarray) and windows.dtype == LA_WINDOW:
+        items = np.ascontiguousarray(windows)
+    else:
+        offs = np.cumsum([0] + [len(r) for r in reads])
+        items = np.zeros(len(windows), dtype=LA_WINDOW)
+        for k, (ri, so, sl, pl, pr, rc) in enumerate(windows):
+            items[k] = (so, offs[ri], sl, pl, pr, len(reads[ri]), rc, 0)
+    n = len(items)
+    buf = np.frombuffer(pool + b"\0", dtype=np.uint8)
+    scores = np.zeros(n, dtype=np.int32)
+    t = LaTiming()
+    need = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.int32)
+    rc = lib.la_align_windows_min(gen.handle, match, mismatch, gap, buf.ctypes.data, len(pool), items.ctypes.data if n else None, n,
+                                  need.ctypes.data if need is not None and n else None, scores.ctypes.data if n else None, ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError("la_align_windows_min failed (%d): %s" % (rc, lib.la_last_error().decode()))
+    return scores, t
+
+
+def window_bytes(data, slice_off, slice_len, pad_left, pad_right, revcomp):
+    """The reference a window stands for, built on the host (the semantics of include/defuse_la.h's la_window)."""
+    w = b"N" * pad_left + bytes(data[slice_off:slice_off + slice_len]) + b"N" * pad_right
+    return w[::-1].translate(_COMPLEMENT) if revcomp else w
+
+
+_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")

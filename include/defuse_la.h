@@ -1,6 +1,6 @@
 /*
  * defuse_la.h — C ABI of the MI355X batched "local realignment" scorer ("la") used by the drop-in
- * `localalign` tool.
+ * `localalign` and `matealign` tools.
  *
  * Replaces SimpleAligner::Align (tools/SimpleAligner.cpp:24-64) for a whole batch of
  * (reference, sequence) pairs: H(i,0) = 0, H(0,j) = j*gap, else
@@ -51,6 +51,35 @@ int la_align_batch(int device, int32_t match, int32_t mismatch, int32_t gap, con
  * soon as nothing in it can still reach the minimum. */
 int la_align_batch_min(int device, int32_t match, int32_t mismatch, int32_t gap, const uint8_t* pool, int64_t pool_len,
                        const la_item* items, int64_t n_items, const int32_t* min_score, int32_t* scores, la_timing* timing);
+
+/* ---- windows cut from a genome in HBM (the drop-in `matealign`, tools/matealign.cpp) ---------------------------------- */
+typedef struct la_genome la_genome;   /* opaque: the concatenated contig bytes on one device */
+
+/* Copies len bytes to the device, exactly as given (no case folding, no recoding).  *out is freed by la_genome_destroy. */
+int la_genome_create(int device, const uint8_t* bytes, int64_t len, la_genome** out);
+void la_genome_destroy(la_genome* genome);
+
+/* The reference of a pair is the window
+ *     'N' x pad_left + genome[slice_off, slice_off + slice_len) + 'N' x pad_right,
+ * reversed as a whole and complemented (A<->T, C<->G, a<->t, c<->g; every other byte, padding included, unchanged) when
+ * revcomp is set: Sequences::Get (tools/Sequences.cpp:60-79) followed by ReverseComplement (tools/Common.cpp:32-54).  The
+ * padding is the byte 'N', which a read's 'N' matches.  The sequence is pool[seq_off, seq_off + seq_len). */
+typedef struct la_window {
+    int64_t slice_off;   /* genome byte offset of the contig slice */
+    int64_t seq_off;     /* read bytes in pool */
+    int32_t slice_len;   /* bytes taken from the genome (may be 0) */
+    int32_t pad_left;    /* 'N' bytes before the slice */
+    int32_t pad_right;   /* 'N' bytes after it */
+    int32_t seq_len;
+    int32_t revcomp;     /* 1: reverse the whole window, complement ACGTacgt only */
+    int32_t pad_;
+} la_window;
+
+/* la_align_batch_min on windows: the same scores, the same 16-bit / int32 selection and the same meaning of min_score (NULL:
+ * every score exact), on the device the genome lives on.  Only the reads and the descriptors cross the bus. */
+int la_align_windows_min(const la_genome* genome, int32_t match, int32_t mismatch, int32_t gap, const uint8_t* pool, int64_t pool_len,
+                         const la_window* windows, int64_t n_windows, const int32_t* min_score, int32_t* scores, la_timing* timing);
+
 const char* la_last_error(void);
 
 #ifdef __cplusplus

@@ -28,6 +28,7 @@
 #include <fstream>
 #include <functional>
 #include <iostream>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -1713,44 +1714,99 @@ struct ReadStorePair {
     bool get(int frag, int end, const char*& s, size_t& n) const { return file[1].get(frag, end, s, n) || file[0].get(frag, end, s, n); }
 };
 
-// FASTQ: tools/ReadStream.cpp:18-32 (extension check), :57-104 (record parsing), AddReads SplitAlignment.cpp:253-264
+// One FASTQ file read record by record: tools/ReadStream.cpp:18-32 (IReadStream::Create: extension check, open) and :57-104
+// (FastqReadStream::GetNextRead).  open() prints what Create prints on err and returns false where it returns no stream; next()
+// returns false at the end of the file and at the first record the reference cannot interpret (after printing its message).
+// The fragment is the text between '@' and the first '/', not yet an integer: the callers convert it where the reference does.
+struct FastqRecord { std::string name, sequence; std::string_view fragment; int end = 0; };
+class FastqReader {
+public:
+    ~FastqReader() { if (f_) fclose(f_); }
+    bool open(const std::string& filename, std::ostream& err)
+    {
+        const size_t dot = filename.find_last_of('.');
+        const std::string ext = filename.substr(dot + 1);
+        if (ext != "fastq" && ext != "fq") {
+            err << "Error: unrecognized extension " << ext << std::endl;
+            return false;
+        }
+        f_ = fopen(filename.c_str(), "rb");
+        if (!f_) {
+            err << "Error: unable to open file " << filename << std::endl;
+            return false;
+        }
+        reader_.reset(new LineReader(f_));
+        return true;
+    }
+    bool next(FastqRecord& r, std::ostream& err)
+    {
+        const char* l;
+        size_t n;
+        if (!reader_ || !reader_->next(l, n)) return false;      // records of four lines; an incomplete one ends the file
+        r.name.assign(l, n);
+        if (!reader_->next(l, n)) return false;
+        r.sequence.assign(l, n);
+        if (!reader_->next(l, n) || !reader_->next(l, n)) return false;
+        if (r.name.empty() || r.name[0] != '@') { err << "Error: Unable to interpret read name " << r.name << std::endl; return false; }
+        const size_t slash = r.name.find_first_of('/');
+        const char endc = (slash != std::string::npos && slash + 1 < r.name.size()) ? r.name[slash + 1] : '\0';
+        if (endc != '1' && endc != '2') { err << "Error: Unable to interpret read end " << r.name << std::endl; return false; }
+        r.fragment = std::string_view(r.name).substr(1, slash - 1);
+        r.end = endc == '1' ? 0 : 1;
+        return true;
+    }
+private:
+    FILE* f_ = nullptr;
+    std::unique_ptr<LineReader> reader_;
+};
+
+// FASTQ into a ReadStore: FastqReader above, AddReads SplitAlignment.cpp:253-264
 // err receives what the reference prints on stderr; a condition on which the reference's process ends (an uncaught
 // bad_lexical_cast, ...) is returned in *fatal instead of ending the process here, so that a caller that reads the FASTQ files
 // beside other work can report things in the reference's order.
 inline bool AddReads(const std::string& filename, ReadStore& reads, std::ostream& err, std::string* fatal)
 {
-    const size_t dot = filename.find_last_of('.');
-    const std::string ext = filename.substr(dot + 1);
-    if (ext != "fastq" && ext != "fq") {
-        err << "Error: unrecognized extension " << ext << std::endl;
-        return false;
-    }
-    FILE* in = fopen(filename.c_str(), "rb");
-    if (!in) {
-        err << "Error: unable to open file " << filename << std::endl;
-        return false;
-    }
-    LineReader reader(in);
-    std::string name, sequence;
-    for (;;) {
-        const char* l;
-        size_t n;
-        if (!reader.next(l, n)) break;                     // records of four lines; an incomplete one ends the file
-        name.assign(l, n);
-        if (!reader.next(l, n)) break;
-        sequence.assign(l, n);
-        if (!reader.next(l, n) || !reader.next(l, n)) break;
-        if (name.empty() || name[0] != '@') { err << "Error: Unable to interpret read name " << name << std::endl; break; }
-        const size_t slash = name.find_first_of('/');
-        const char endc = (slash != std::string::npos && slash + 1 < name.size()) ? name[slash + 1] : '\0';
-        if (endc != '1' && endc != '2') { err << "Error: Unable to interpret read end " << name << std::endl; break; }
+    FastqReader in;
+    if (!in.open(filename, err)) return false;
+    FastqRecord r;
+    while (in.next(r, err)) {
         int frag;
-        if (!field_int(name.data() + 1, slash - 1, frag)) { *fatal = "Error: bad integer '" + name.substr(1, slash - 1) + "' in read name " + name; break; }
-        if (sequence.size() >= ((size_t)1 << 24)) { *fatal = "Error: read longer than 16 M bases: " + name; break; }
-        reads.put(frag, endc == '1' ? 0 : 1, sequence.data(), sequence.size());
+        if (!field_int(r.fragment.data(), r.fragment.size(), frag)) { *fatal = "Error: bad integer '" + std::string(r.fragment) + "' in read name " + r.name; break; }
+        if (r.sequence.size() >= ((size_t)1 << 24)) { *fatal = "Error: read longer than 16 M bases: " + r.name; break; }
+        reads.put(frag, r.end, r.sequence.data(), r.sequence.size());
     }
-    fclose(in);
     return fatal->empty();
+}
+
+// ---- scores against a percent-perfect threshold (tools/localalign.cpp:84-92, tools/matealign.cpp:191-201) ---------------------
+// maxScore = len(sequence) * match (a size_t product stored in an int), percent = (double) score / maxScore, and a line is printed
+// unless percent < threshold.
+inline int score_max(size_t seq_len, int matchScore) { return (int)(seq_len * (size_t)matchScore); }
+
+// the smallest score a line needs to be printed at all: below it the device may stop early (la_align_batch_min's min_score)
+inline int32_t threshold_min_score(int maxScore, double threshold)
+{
+    int32_t s = std::numeric_limits<int32_t>::min();
+    if (maxScore > 0 && threshold > 0.0) {
+        s = (int32_t)std::min<double>(std::ceil(threshold * (double)maxScore), 2147483000.0);
+        while (s > 0 && !((double)(s - 1) / (double)maxScore < threshold)) --s;     // exactly the test of the line filter
+        while ((double)s / (double)maxScore < threshold) ++s;
+    }
+    return s;
+}
+
+// appends `id \t score \t percent` (operator<<(double): %g, six significant digits) unless percent < threshold
+inline void append_score_line(std::string& out, std::string_view id, int score, int maxScore, double threshold)
+{
+    const double percent = (double)score / (double)maxScore;
+    if (percent < threshold) return;
+    char num[40];
+    out.append(id.data(), id.size());
+    out += '\t';
+    append_int(out, score);
+    out += '\t';
+    out.append(num, (size_t)snprintf(num, sizeof num, "%g", percent));
+    out += '\n';
 }
 
 // The reads of one FASTQ file by ReadID, built by a team of threads from the mapped file: the same records, messages and

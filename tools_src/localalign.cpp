@@ -7,8 +7,6 @@
 #include "../include/defuse_la.h"
 #include "defuse_host.hpp"
 
-#include <limits>
-
 using namespace defuse;
 
 namespace {
@@ -27,33 +25,14 @@ void flush(Batch& b, int matchScore, int misMatchScore, int gapScore, double thr
     std::vector<int32_t> scores(b.items.size());
     // the smallest score a line needs to be printed at all: below it the device may stop early
     std::vector<int32_t> need(b.items.size());
-    for (size_t k = 0; k < b.items.size(); ++k) {
-        const int maxScore = (size_t)b.items[k].seq_len * matchScore;
-        int32_t s = std::numeric_limits<int32_t>::min();
-        if (maxScore > 0 && threshold > 0.0) {
-            s = (int32_t)std::min<double>(std::ceil(threshold * (double)maxScore), 2147483000.0);
-            while (s > 0 && !((double)(s - 1) / (double)maxScore < threshold)) --s;     // exactly the test of :89
-            while ((double)s / (double)maxScore < threshold) ++s;
-        }
-        need[k] = s;
-    }
+    for (size_t k = 0; k < b.items.size(); ++k) need[k] = threshold_min_score(score_max((size_t)b.items[k].seq_len, matchScore), threshold);
     const int device = dsa_pick_device();                  // as the other tools: DEFUSE_GPU, else pid mod device count
     if (la_align_batch_min(device, matchScore, misMatchScore, gapScore, b.pool.data(), (int64_t)b.pool.size(), b.items.data(),
                            (int64_t)b.items.size(), need.data(), scores.data(), nullptr) != 0)
         die(std::string("Error: GPU alignment failed: ") + la_last_error());
     std::string out;
-    char num[40];
     for (size_t k = 0; k < b.items.size(); ++k) {
-        const int score = scores[k];
-        const int maxScore = (size_t)b.items[k].seq_len * matchScore;      // tools/localalign.cpp:86
-        const double percent = (double)score / (double)maxScore;
-        if (percent < threshold) continue;
-        out += b.ids[k];
-        out += '\t';
-        append_int(out, score);
-        out += '\t';
-        out.append(num, (size_t)snprintf(num, sizeof num, "%g", percent));   // operator<<(double): six significant digits
-        out += '\n';
+        append_score_line(out, b.ids[k], scores[k], score_max((size_t)b.items[k].seq_len, matchScore), threshold);  // tools/localalign.cpp:84-92
         if (out.size() > (1u << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
     }
     fwrite(out.data(), 1, out.size(), stdout);
