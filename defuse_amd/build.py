@@ -37,9 +37,19 @@ LIB_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared"]
 DSA_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 
 
+def api_headers():
+    """include/defuse_*.h, one per module of the C ABI."""
+    inc = os.path.join(ROOT, "include")
+    return [os.path.join(inc, h) for h in sorted(os.listdir(inc)) if h.startswith("defuse_") and h.endswith(".h")]
+
+
+def api_sources():
+    """csrc/*_api.hip but dsa_api.hip, which is compiled on its own with DSA_FLAGS (compile_lib)."""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith("_api.hip") and f != "dsa_api.hip"]
+
+
 def lib_sources():
-    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + \
-           [os.path.join(ROOT, "include", h) for h in ("defuse_dsa.h", "defuse_sc.h", "defuse_mpe.h", "defuse_la.h", "defuse_hc.h", "defuse_cov.h", "defuse_cmp.h", "defuse_est.h")]
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + api_headers()
 
 
 _dsa_flags_probe = {}
@@ -109,8 +119,7 @@ def compile_lib(out, extra_flags=()):
     tmp_out = out + tag
     try:
         _run([HIPCC] + [f for f in LIB_FLAGS if f != "-shared"] + dsa_flags + extra + define + ["-c", "-o", obj, os.path.join(CSRC, "dsa_api.hip")])
-        _run([HIPCC] + LIB_FLAGS + extra + define + ["-o", tmp_out, obj] +
-             [os.path.join(CSRC, f) for f in ("sc_api.hip", "mpe_api.hip", "la_api.hip", "hc_api.hip", "cov_api.hip", "cmp_api.hip", "est_api.hip")])
+        _run([HIPCC] + LIB_FLAGS + extra + define + ["-o", tmp_out, obj] + api_sources())
         os.replace(tmp_out, out)
     finally:
         for f in (obj, tmp_out):
@@ -122,6 +131,11 @@ def compile_lib(out, extra_flags=()):
 TOOLS = ["dosplitalign", "evalsplitalign", "setcover", "clustermatepairs", "localalign", "defuse_glue", "calccov", "matealign", "estislands"]
 
 
+def tool_deps(src, lib):
+    """What a tool binary is rebuilt for: its source, the shared host headers, the C-ABI headers and the library."""
+    return [src] + [os.path.join(ROOT, "tools_src", h) for h in ("defuse_host.hpp", "evaluate.hpp", "task_cache.hpp")] + api_headers() + [lib]
+
+
 def build_tools(force=False):
     """The drop-in tool binaries (C++17 host code on the C ABI) -> bin/."""
     bindir = os.path.join(ROOT, "bin")
@@ -131,12 +145,7 @@ def build_tools(force=False):
     for t in TOOLS:
         src = os.path.join(ROOT, "tools_src", t + ".cpp")
         out = os.path.join(bindir, t)
-        deps = [src, os.path.join(ROOT, "tools_src", "defuse_host.hpp"), os.path.join(ROOT, "tools_src", "evaluate.hpp"),
-                os.path.join(ROOT, "tools_src", "task_cache.hpp"), os.path.join(ROOT, "include", "defuse_dsa.h"),
-                os.path.join(ROOT, "include", "defuse_sc.h"), os.path.join(ROOT, "include", "defuse_mpe.h"),
-                os.path.join(ROOT, "include", "defuse_la.h"), os.path.join(ROOT, "include", "defuse_cov.h"),
-                os.path.join(ROOT, "include", "defuse_cmp.h"), os.path.join(ROOT, "include", "defuse_est.h"), lib]
-        if force or _newer(out, deps):
+        if force or _newer(out, tool_deps(src, lib)):
             if t == "dosplitalign":          # opens the C-ABI library at run time (on a helper thread), see tools_src/dosplitalign.cpp
                 _run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-pthread", "-o", out, src, "-ldl"])
             else:
@@ -158,8 +167,7 @@ def build_sanitized(kind, force=False):
     for t in TOOLS:
         src = os.path.join(ROOT, "tools_src", t + ".cpp")
         out = os.path.join(bindir, t)
-        if force or _newer(out, [src, os.path.join(ROOT, "tools_src", "defuse_host.hpp"), os.path.join(ROOT, "tools_src", "evaluate.hpp"),
-                                 os.path.join(ROOT, "tools_src", "task_cache.hpp"), lib]):
+        if force or _newer(out, tool_deps(src, lib)):
             cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread"] + flags + ["-o", out, src]
             cmd += ["-ldl"] if t == "dosplitalign" else [lib, "-Wl,-rpath,$ORIGIN/../../defuse_amd"]
             _run(cmd)

@@ -16,29 +16,22 @@
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/defuse_cmp.h"
 #include "../../include/defuse_dsa.h"
-#include "hip_raii.hpp"
+#include "hip_host.hpp"
 
 namespace {
 
+using hiphost::DeviceBuffer;
+using hiphost::grid_of;
+
 thread_local std::string g_cmp_err;
 
-#define CMP_HIP(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            char b_[256];                                                                         \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            g_cmp_err = b_;                                                                       \
-            return DSA_E_DEVICE;                                                                  \
-        }                                                                                         \
-    } while (0)
+#define CMP_HIP(call) HIPHOST_TRY(g_cmp_err, call)
 
 constexpr int BIN_LENGTH = 1 << 15;            // tools/clustermatepairs.cpp:385 (binLength)
 constexpr uint32_t REF_MASK = 0x0FFFFFFFu;
@@ -218,27 +211,11 @@ __global__ void k_cmp_same_keys(const unsigned long long* __restrict__ a, const 
     if (i < n && a[i] != b[i]) globals[2] = 1;
 }
 
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    ~DBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
-
 struct Side {
-    DBuf<unsigned long long> key, key_sorted, uniq;
-    DBuf<cmp_packed> pay, pay_sorted;
-    DBuf<uint32_t> idx, idx_sorted, off;
-    DBuf<int> run_len;
+    DeviceBuffer<unsigned long long> key, key_sorted, uniq;
+    DeviceBuffer<cmp_packed> pay, pay_sorted;
+    DeviceBuffer<uint32_t> idx, idx_sorted, off;
+    DeviceBuffer<int> run_len;
     int64_t n = 0;
 };
 
@@ -246,14 +223,14 @@ struct Side {
 
 struct cmp_binner {
     int device = -1;
-    hipraii::Stream st;
-    hipraii::Event ev[2];
+    hiphost::Stream st;
+    hiphost::Event ev[2];
     int64_t n_records = 0, n_fragments = 0;
-    DBuf<cmp_record> recs;
-    DBuf<uint32_t> frag_start, cnt[4], off_first, off_second;
-    DBuf<unsigned long long> globals;
-    DBuf<uint8_t> tmp;
-    DBuf<int> n_runs;
+    DeviceBuffer<cmp_record> recs;
+    DeviceBuffer<uint32_t> frag_start, cnt[4], off_first, off_second;
+    DeviceBuffer<unsigned long long> globals;
+    DeviceBuffer<uint8_t> tmp;
+    DeviceBuffer<int> n_runs;
     Side side[2];
     int64_t n_keys = 0;
     bool ran = false;
@@ -267,8 +244,7 @@ int cmp_bin_create(cmp_binner** out, int device)
 {
     if (!out) return DSA_E_ARG;
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { g_cmp_err = "no usable HIP device"; return DSA_E_DEVICE; }
+    if (hiphost::check_device(device, &g_cmp_err)) return DSA_E_DEVICE;
     CMP_HIP(hipSetDevice(device));
     cmp_binner* b = new cmp_binner();
     b->device = device;
@@ -335,7 +311,7 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
     const unsigned long long init[4] = {~0ull, 0, 0, 0};
     CMP_HIP(hipMemcpyAsync(b->globals.p, init, sizeof init, hipMemcpyHostToDevice, st));
     CMP_HIP(hipEventRecord(b->ev[0], st));
-    const unsigned grid = (unsigned)((nf + 255) / 256);
+    const unsigned grid = grid_of(nf);
     if (nf) {
         hipLaunchKernelGGL(k_cmp_count, dim3(grid), dim3(256), 0, st, b->recs.p, b->frag_start.p, nf, (int)mfr, b->cnt[0].p, b->cnt[1].p, b->cnt[2].p,
                            b->cnt[3].p, b->globals.p);
@@ -345,12 +321,10 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
         CMP_HIP(hipMemsetAsync(b->cnt[0].p, 0, sizeof(uint32_t), st));
         CMP_HIP(hipMemsetAsync(b->cnt[1].p, 0, sizeof(uint32_t), st));
     }
-    size_t tmp_bytes = 0, need = 0;
-    CMP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, b->cnt[0].p, b->off_first.p, (int)(nf + 1), st));
-    CMP_HIP(b->tmp.reserve(tmp_bytes));
-    need = b->tmp.cap;
-    CMP_HIP(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, need, b->cnt[0].p, b->off_first.p, (int)(nf + 1), st));
-    need = b->tmp.cap;
+    CMP_HIP(hiphost::cub_run(b->tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tb, b->cnt[0].p, b->off_first.p, (int)(nf + 1), st);
+    }));
+    size_t need = b->tmp.cap;               // the second scan has the same shape: the temp buffer serves it as it is
     CMP_HIP(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, need, b->cnt[1].p, b->off_second.p, (int)(nf + 1), st));
     uint32_t totals[2] = {0, 0};
     unsigned long long glob[4];
@@ -393,32 +367,26 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
         Side& S = b->side[s];
         const int n = (int)S.n;
         if (n == 0) continue;
-        hipLaunchKernelGGL(k_cmp_iota, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S.idx.p, (int64_t)n);
+        hipLaunchKernelGGL(k_cmp_iota, dim3(grid_of(n)), dim3(256), 0, st, S.idx.p, (int64_t)n);
         // stable: entries with one key keep the order they were written in, which is the reference's order of appends
-        size_t tb = 0;
-        CMP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, S.key.p, S.key_sorted.p, S.idx.p, S.idx_sorted.p, n, 0, 64, st));
-        CMP_HIP(b->tmp.reserve(tb));
-        tb = b->tmp.cap;
-        CMP_HIP(hipcub::DeviceRadixSort::SortPairs(b->tmp.p, tb, S.key.p, S.key_sorted.p, S.idx.p, S.idx_sorted.p, n, 0, 64, st));
-        hipLaunchKernelGGL(k_cmp_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S.pay.p, S.idx_sorted.p, S.pay_sorted.p, (int64_t)n);
-        tb = 0;
-        CMP_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, tb, S.key_sorted.p, S.uniq.p, S.run_len.p, b->n_runs.p + s, n, st));
-        CMP_HIP(b->tmp.reserve(tb));
-        tb = b->tmp.cap;
-        CMP_HIP(hipcub::DeviceRunLengthEncode::Encode(b->tmp.p, tb, S.key_sorted.p, S.uniq.p, S.run_len.p, b->n_runs.p + s, n, st));
+        CMP_HIP(hiphost::cub_run(b->tmp, [&](void* t, size_t& tb) {
+            return hipcub::DeviceRadixSort::SortPairs(t, tb, S.key.p, S.key_sorted.p, S.idx.p, S.idx_sorted.p, n, 0, 64, st);
+        }));
+        hipLaunchKernelGGL(k_cmp_gather, dim3(grid_of(n)), dim3(256), 0, st, S.pay.p, S.idx_sorted.p, S.pay_sorted.p, (int64_t)n);
+        CMP_HIP(hiphost::cub_run(b->tmp, [&](void* t, size_t& tb) {
+            return hipcub::DeviceRunLengthEncode::Encode(t, tb, S.key_sorted.p, S.uniq.p, S.run_len.p, b->n_runs.p + s, n, st);
+        }));
         CMP_HIP(hipMemcpyAsync(&runs[s], b->n_runs.p + s, sizeof(int), hipMemcpyDeviceToHost, st));
         CMP_HIP(hipStreamSynchronize(st));
         CMP_HIP(hipMemsetAsync(S.run_len.p + runs[s], 0, sizeof(int), st));
-        tb = 0;
-        CMP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, S.run_len.p, (int*)S.off.p, runs[s] + 1, st));
-        CMP_HIP(b->tmp.reserve(tb));
-        tb = b->tmp.cap;
-        CMP_HIP(hipcub::DeviceScan::ExclusiveSum(b->tmp.p, tb, S.run_len.p, (int*)S.off.p, runs[s] + 1, st));
+        CMP_HIP(hiphost::cub_run(b->tmp, [&](void* t, size_t& tb) {
+            return hipcub::DeviceScan::ExclusiveSum(t, tb, S.run_len.p, (int*)S.off.p, runs[s] + 1, st);
+        }));
     }
     // every bin pair has entries on both sides (each insert() pair of the reference feeds both lists)
     if (runs[0] != runs[1]) { g_cmp_err = "internal: the two sides disagree on the bin pairs"; return DSA_E_DEVICE; }
     if (runs[0])
-        hipLaunchKernelGGL(k_cmp_same_keys, dim3((unsigned)((runs[0] + 255) / 256)), dim3(256), 0, st, b->side[0].uniq.p, b->side[1].uniq.p, (int64_t)runs[0], b->globals.p);
+        hipLaunchKernelGGL(k_cmp_same_keys, dim3(grid_of(runs[0])), dim3(256), 0, st, b->side[0].uniq.p, b->side[1].uniq.p, (int64_t)runs[0], b->globals.p);
     CMP_HIP(hipEventRecord(b->ev[1], st));
     CMP_HIP(hipMemcpyAsync(glob, b->globals.p, sizeof glob, hipMemcpyDeviceToHost, st));
     CMP_HIP(hipStreamSynchronize(st));
@@ -428,7 +396,7 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
     stats->n_keys = runs[0];
     stats->n_first = b->side[0].n;
     stats->n_second = b->side[1].n;
-    (void)hipEventElapsedTime(&stats->device_ms, b->ev[0], b->ev[1]);
+    stats->device_ms = hiphost::elapsed(b->ev[0], b->ev[1]);
     b->ran = true;
     return DSA_OK;
 }

@@ -8,50 +8,20 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cstdarg>
-#include <cstdio>
 #include <string>
 
 #include "../../include/defuse_cov.h"
 #include "../../include/defuse_dsa.h"
+#include "hip_host.hpp"
 
 namespace {
 
+using hiphost::DeviceBuffer;
+using hiphost::fail;
+
 thread_local std::string g_cov_err;
 
-int cov_fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_cov_err = buf;
-    return code;
-}
-
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
-};
-struct Stream {
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Stream()
-    {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-
-#define COV_HIP(call)                                                                                              \
-    do {                                                                                                           \
-        hipError_t e_ = (call);                                                                                    \
-        if (e_ != hipSuccess) return cov_fail(DSA_E_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define COV_HIP(call) HIPHOST_TRY(g_cov_err, call)
 
 struct Ranges { int us, ue, as[2], ae[2]; };
 __device__ __forceinline__ Ranges ranges_of(const cov_fragment& f, int trim, int anchor)
@@ -135,47 +105,47 @@ int cov_sample_batch(int device, const int64_t* ref_sample_off, int32_t n_refs, 
                      int32_t* split_idx, double* split_pos, double* split_min, int64_t split_cap, int64_t* n_split,
                      cov_timing* timing)
 {
-    if (n_refs < 0 || n_fragments < 0 || !n_length || !n_split) return cov_fail(DSA_E_ARG, "bad arguments");
+    if (n_refs < 0 || n_fragments < 0 || !n_length || !n_split) return fail(g_cov_err, DSA_E_ARG, "bad arguments");
     *n_length = *n_split = 0;
     if (timing) *timing = cov_timing{};
     if (n_fragments == 0) return DSA_OK;
-    if (!ref_sample_off || !fragments) return cov_fail(DSA_E_ARG, "null pointer with non-zero size");
+    if (!ref_sample_off || !fragments) return fail(g_cov_err, DSA_E_ARG, "null pointer with non-zero size");
     const int64_t n_samples = ref_sample_off[n_refs];
     for (int32_t r = 0; r < n_refs; ++r)
-        if (ref_sample_off[r] > ref_sample_off[r + 1]) return cov_fail(DSA_E_ARG, "ref_sample_off is not ascending");
-    if (n_samples >= ((int64_t)1 << 31)) return cov_fail(DSA_E_LIMIT, "more than 2^31-1 samples");
+        if (ref_sample_off[r] > ref_sample_off[r + 1]) return fail(g_cov_err, DSA_E_ARG, "ref_sample_off is not ascending");
+    if (n_samples >= ((int64_t)1 << 31)) return fail(g_cov_err, DSA_E_LIMIT, "more than 2^31-1 samples");
     for (int64_t i = 0; i < n_fragments; ++i)
-        if (fragments[i].ref < 0 || fragments[i].ref >= n_refs) return cov_fail(DSA_E_ARG, "fragment %lld: bad transcript index", (long long)i);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return cov_fail(DSA_E_DEVICE, "no HIP device %d", device);
+        if (fragments[i].ref < 0 || fragments[i].ref >= n_refs) return fail(g_cov_err, DSA_E_ARG, "fragment %lld: bad transcript index", (long long)i);
+    if (hiphost::check_device(device, &g_cov_err)) return DSA_E_DEVICE;
     COV_HIP(hipSetDevice(device));
-    Stream st;
+    hiphost::Stream st;
+    hiphost::Event e0, e1;
     COV_HIP(hipStreamCreate(&st.s));
-    COV_HIP(hipEventCreate(&st.e0));
-    COV_HIP(hipEventCreate(&st.e1));
-    DBuf<int64_t> d_off, d_nl, d_ns, d_al, d_as;
-    DBuf<int32_t> d_pos;
-    DBuf<cov_fragment> d_fr;
-    DBuf<uint8_t> d_tmp;
-    COV_HIP(d_off.alloc((size_t)n_refs + 1));
-    COV_HIP(d_pos.alloc((size_t)n_samples));
-    COV_HIP(d_fr.alloc((size_t)n_fragments));
-    COV_HIP(d_nl.alloc((size_t)n_fragments + 1));
-    COV_HIP(d_ns.alloc((size_t)n_fragments + 1));
-    COV_HIP(d_al.alloc((size_t)n_fragments + 1));
-    COV_HIP(d_as.alloc((size_t)n_fragments + 1));
+    COV_HIP(e0.create());
+    COV_HIP(e1.create());
+    DeviceBuffer<int64_t> d_off, d_nl, d_ns, d_al, d_as;
+    DeviceBuffer<int32_t> d_pos;
+    DeviceBuffer<cov_fragment> d_fr;
+    DeviceBuffer<uint8_t> d_tmp;
+    COV_HIP(d_off.reserve((size_t)n_refs + 1));
+    COV_HIP(d_pos.reserve((size_t)n_samples));
+    COV_HIP(d_fr.reserve((size_t)n_fragments));
+    COV_HIP(d_nl.reserve((size_t)n_fragments + 1));
+    COV_HIP(d_ns.reserve((size_t)n_fragments + 1));
+    COV_HIP(d_al.reserve((size_t)n_fragments + 1));
+    COV_HIP(d_as.reserve((size_t)n_fragments + 1));
     COV_HIP(hipMemcpyAsync(d_off.p, ref_sample_off, ((size_t)n_refs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st.s));
     if (n_samples) COV_HIP(hipMemcpyAsync(d_pos.p, sample_pos, (size_t)n_samples * sizeof(int32_t), hipMemcpyHostToDevice, st.s));
     COV_HIP(hipMemcpyAsync(d_fr.p, fragments, (size_t)n_fragments * sizeof(cov_fragment), hipMemcpyHostToDevice, st.s));
     COV_HIP(hipMemsetAsync(d_nl.p + n_fragments, 0, sizeof(int64_t), st.s));
     COV_HIP(hipMemsetAsync(d_ns.p + n_fragments, 0, sizeof(int64_t), st.s));
-    const unsigned grid = (unsigned)((n_fragments + 255) / 256);
-    COV_HIP(hipEventRecord(st.e0, st.s));
+    const unsigned grid = hiphost::grid_of(n_fragments);
+    COV_HIP(hipEventRecord(e0, st.s));
     hipLaunchKernelGGL(k_cov_count, dim3(grid), dim3(256), 0, st.s, d_fr.p, n_fragments, d_off.p, d_pos.p, trim_length, split_min_anchor, d_nl.p, d_ns.p);
-    size_t tmp = 0;
-    COV_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, d_nl.p, d_al.p, (int)(n_fragments + 1), st.s));
-    COV_HIP(d_tmp.alloc(tmp));
-    COV_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_nl.p, d_al.p, (int)(n_fragments + 1), st.s));
+    COV_HIP(hiphost::cub_run(d_tmp, [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::ExclusiveSum(t, b, d_nl.p, d_al.p, (int)(n_fragments + 1), st.s);
+    }));
+    size_t tmp = d_tmp.cap;                  // the second scan has the same shape: the temp buffer serves it as it is
     COV_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp, d_ns.p, d_as.p, (int)(n_fragments + 1), st.s));
     int64_t totals[2] = {0, 0};
     COV_HIP(hipMemcpyAsync(&totals[0], d_al.p + n_fragments, sizeof(int64_t), hipMemcpyDeviceToHost, st.s));
@@ -185,19 +155,19 @@ int cov_sample_batch(int device, const int64_t* ref_sample_off, int32_t n_refs, 
     *n_length = totals[0];
     *n_split = totals[1];
     if (totals[0] > length_cap || totals[1] > split_cap)
-        return cov_fail(DSA_E_CAPACITY, "need room for %lld length and %lld split samples", (long long)totals[0], (long long)totals[1]);
+        return fail(g_cov_err, DSA_E_CAPACITY, "need room for %lld length and %lld split samples", (long long)totals[0], (long long)totals[1]);
     if ((totals[0] && (!length_idx || !length_val)) || (totals[1] && (!split_idx || !split_pos || !split_min)))
-        return cov_fail(DSA_E_ARG, "null output");
-    DBuf<int32_t> d_li, d_lv, d_si;
-    DBuf<double> d_sp, d_sm;
-    COV_HIP(d_li.alloc((size_t)totals[0]));
-    COV_HIP(d_lv.alloc((size_t)totals[0]));
-    COV_HIP(d_si.alloc((size_t)totals[1]));
-    COV_HIP(d_sp.alloc((size_t)totals[1]));
-    COV_HIP(d_sm.alloc((size_t)totals[1]));
+        return fail(g_cov_err, DSA_E_ARG, "null output");
+    DeviceBuffer<int32_t> d_li, d_lv, d_si;
+    DeviceBuffer<double> d_sp, d_sm;
+    COV_HIP(d_li.reserve((size_t)totals[0]));
+    COV_HIP(d_lv.reserve((size_t)totals[0]));
+    COV_HIP(d_si.reserve((size_t)totals[1]));
+    COV_HIP(d_sp.reserve((size_t)totals[1]));
+    COV_HIP(d_sm.reserve((size_t)totals[1]));
     hipLaunchKernelGGL(k_cov_write, dim3(grid), dim3(256), 0, st.s, d_fr.p, n_fragments, d_off.p, d_pos.p, trim_length, split_min_anchor,
                        d_al.p, d_as.p, d_li.p, d_lv.p, d_si.p, d_sp.p, d_sm.p);
-    COV_HIP(hipEventRecord(st.e1, st.s));
+    COV_HIP(hipEventRecord(e1, st.s));
     if (totals[0]) {
         COV_HIP(hipMemcpyAsync(length_idx, d_li.p, (size_t)totals[0] * sizeof(int32_t), hipMemcpyDeviceToHost, st.s));
         COV_HIP(hipMemcpyAsync(length_val, d_lv.p, (size_t)totals[0] * sizeof(int32_t), hipMemcpyDeviceToHost, st.s));
@@ -210,9 +180,7 @@ int cov_sample_batch(int device, const int64_t* ref_sample_off, int32_t n_refs, 
     COV_HIP(hipStreamSynchronize(st.s));
     COV_HIP(hipGetLastError());
     if (timing) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, st.e0, st.e1);
-        timing->kernel_ms = ms;
+        timing->kernel_ms = hiphost::elapsed(e0, e1);
         timing->n_length_samples = totals[0];
         timing->n_split_samples = totals[1];
     }

@@ -15,7 +15,6 @@
 #include <memory>
 #include <mutex>
 #include <thread>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,37 +25,17 @@
 #include "dsa_kernels.hpp"
 #include "dsa_long.hpp"
 #include "dsa_diag_host.hpp"
+#include "hip_host.hpp"
 
 using namespace dsa;
 
 namespace {
 
+// per-context and per-lane buffers grow with some slack (hiphost::GrowSize)
 template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;   // elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+using DevBuf = hiphost::DeviceBuffer<T, hiphost::GrowSize>;
+using hiphost::elapsed;
+using hiphost::grid_of;
 
 struct HostResult {            // pinned: filled by k_publish at the end of a slice's first phase
     Counters ctr;
@@ -201,26 +180,15 @@ hipStream_t dsa_ctx::main_stream() const { return lanes->lane[0].stream; }
 
 namespace {
 
-int fail(dsa_ctx* c, int code, const char* fmt, ...)
+// the message goes to the context, if there is one (dsa_download and its kin are called with what the caller has)
+template <class... Args>
+int fail(dsa_ctx* c, int code, const char* fmt, Args... args)
 {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
+    std::string nowhere;
+    return hiphost::fail(c ? c->err : nowhere, code, fmt, args...);
 }
 
-#define HIPC(call)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return fail(ctx, DSA_E_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                                       \
-    } while (0)
-
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+#define HIPC(call) HIPHOST_TRY(ctx->err, call)
 
 // minScore exactly as the reference writes it (tools/SplitAlignment.cpp:379):
 // (int)((float)len * (float)matchScore * 0.90)
@@ -314,7 +282,7 @@ int enqueue_plan(dsa_ctx* ctx)
         PlanGlobals* glob = ctx->plan_glob.p + k;
         if (!no_reorder) {
             HIPC(hipMemsetAsync(ctx->plan_runs.p, 0, (size_t)nf * sizeof(PlanRun), st));
-            hipLaunchKernelGGL(k_plan_runs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, n, ctx->plan_runs.p);
+            hipLaunchKernelGGL(k_plan_runs, dim3(grid_of(n)), dim3(256), 0, st, in, n, ctx->plan_runs.p);
             PlanParams pp = prm;
             pp.use_rank = no_rank ? 0 : 1;
             pp.use_bound = no_tighten ? 0 : 1;
@@ -328,7 +296,7 @@ int enqueue_plan(dsa_ctx* ctx)
             hipLaunchKernelGGL(k_plan_place_b, dim3((unsigned)nb), dim3(PLACE_BLOCK), 0, st, ctx->plan_order.p, ctx->plan_runs.p, nf, ctx->plan_bsum.p,
                                ctx->plan_start.p, ctx->plan_flip.p);
         }
-        hipLaunchKernelGGL(k_plan_permute, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, n, ctx->d_fusions.p, ctx->plan_runs.p, ctx->plan_start.p,
+        hipLaunchKernelGGL(k_plan_permute, dim3(grid_of(n)), dim3(256), 0, st, in, n, ctx->d_fusions.p, ctx->plan_runs.p, ctx->plan_start.p,
                            ctx->plan_flip.p, ctx->plan_rank.p, ctx->plan_bound.p, glob, no_reorder ? 1 : 0, ctx->d_pairs.p + sl.pair_begin,
                            ctx->d_orig.p + sl.pair_begin);
     }
@@ -341,18 +309,10 @@ int enqueue_plan(dsa_ctx* ctx)
 
 int exclusive_scan(dsa_ctx* ctx, PipeLane& L, const int64_t* in, int64_t* out, int64_t n)
 {
-    size_t tmp = 0;
-    HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (int)n, L.stream));
-    HIPC(L.d_scan_tmp.reserve(tmp));
-    HIPC(hipcub::DeviceScan::ExclusiveSum(L.d_scan_tmp.p, tmp, in, out, (int)n, L.stream));
+    HIPC(hiphost::cub_run(L.d_scan_tmp, [&](void* t, size_t& tmp) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tmp, in, out, (int)n, L.stream);
+    }));
     return DSA_OK;
-}
-
-float elapsed(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
 }
 
 int grow_records(dsa_ctx* ctx, size_t need)
@@ -364,8 +324,7 @@ int grow_records(dsa_ctx* ctx, size_t need)
     if (ctx->n_records)
         HIPC(hipMemcpy(bigger.p, ctx->d_records.p, ctx->n_records * sizeof(dsa_record), hipMemcpyDeviceToDevice));
     ctx->d_records.release();
-    std::swap(ctx->d_records.p, bigger.p);
-    std::swap(ctx->d_records.cap, bigger.cap);
+    ctx->d_records.swap(bigger);
     return DSA_OK;
 }
 
@@ -681,9 +640,7 @@ static int create_ctx(dsa_ctx** out, int device, dsa_ctx* share)
 {
     if (!out) return DSA_E_ARG;
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return DSA_E_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return DSA_E_DEVICE;
+    if (hiphost::check_device(device) || hipSetDevice(device) != hipSuccess) return DSA_E_DEVICE;
     dsa_ctx* ctx = new dsa_ctx();
     ctx->device = device;
     bool ok = true;
@@ -818,7 +775,7 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
             ctx->h_long_fusions.push_back(f);
             continue;
         }
-        nch_all = std::max(nch_all, std::max(cdiv(fu.ref0_len, W), cdiv(fu.ref1_len, W)));
+        nch_all = std::max<int>(nch_all, std::max(grid_of(fu.ref0_len, W), grid_of(fu.ref1_len, W)));
         maxwin = std::max(maxwin, std::max(fu.ref0_len, fu.ref1_len));
     }
     const bool any_long_fusion = !ctx->h_long_fusions.empty();
@@ -877,7 +834,7 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
         if (nl) HIPC(hipMemcpyAsync(ctx->d_long.p, ctx->h_long.data(), (size_t)nl * sizeof(LongDesc), hipMemcpyHostToDevice, st));
         if (nlf) HIPC(hipMemcpyAsync(ctx->d_long_fusions.p, ctx->h_long_fusions.data(), (size_t)nlf * sizeof(int32_t), hipMemcpyHostToDevice, st));
         const int n = std::max(nl, nlf);
-        hipLaunchKernelGGL(k_long_blank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ctx->d_pairs_in.p, ctx->d_long.p, nl, ctx->d_fusions.p,
+        hipLaunchKernelGGL(k_long_blank, dim3(grid_of(n)), dim3(256), 0, st, ctx->d_pairs_in.p, ctx->d_long.p, nl, ctx->d_fusions.p,
                            ctx->d_long_fusions.p, nlf);
     }
     std::vector<int32_t>& tab = ctx->h_min_score;       // lives as long as the copy may be in flight
@@ -1001,7 +958,7 @@ int run_slices(dsa_ctx* ctx)
         Geom g = ctx->slices[0].g;
         const int64_t total = (int64_t)g.n_fusions * g.lrp;
         HIPC(hipEventRecord(ctx->ev_pack[0], L0.stream));
-        hipLaunchKernelGGL(k_pack_refs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, L0.stream, ctx->d_ref.p, ctx->d_fusions.p,
+        hipLaunchKernelGGL(k_pack_refs, dim3(grid_of(total)), dim3(256), 0, L0.stream, ctx->d_ref.p, ctx->d_fusions.p,
                            ctx->d_refcodes.p, g);
         if (ns > 1) {       // lane 1 waits for the codes; a run of one slice times the pack up to the start of its fill instead
             HIPC(hipEventRecord(ctx->ev_pack[1], L0.stream));

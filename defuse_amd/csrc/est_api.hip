@@ -32,48 +32,25 @@
 #include <hipcub/hipcub.hpp>
 
 #include <climits>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/defuse_dsa.h"
 #include "../../include/defuse_est.h"
-#include "hip_raii.hpp"
+#include "hip_host.hpp"
 
 namespace {
 
+using hiphost::DeviceBuffer;
+using hiphost::grid_of;
+
 thread_local std::string g_est_err;
 
-#define EST_HIP(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            char b_[256];                                                                         \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            g_est_err = b_;                                                                       \
-            return DSA_E_DEVICE;                                                                  \
-        }                                                                                         \
-    } while (0)
+#define EST_HIP(call) HIPHOST_TRY(g_est_err, call)
 
 constexpr int BLOCK = 256;
 constexpr long long NEG_INF = LLONG_MIN;
-
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    ~DBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-};
 
 // an element of the segmented running max: a head starts a new segment
 struct SegMax {
@@ -240,21 +217,19 @@ __global__ void k_est_lookup(const int32_t* __restrict__ is, const int32_t* __re
     out[q] = res;
 }
 
-inline unsigned grid_of(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 }  // namespace
 
 struct est_catalog {
     int device = -1;
     int n_chrom = 0;
-    hipraii::Stream st;
-    hipraii::Event ev[2];
+    hiphost::Stream st;
+    hiphost::Event ev[2];
     int64_t n_segments = 0, n_degenerate = 0, n_islands = 0;
     float build_ms = 0;
-    DBuf<int32_t> is, ie;
-    DBuf<int64_t> chrom_off;
-    DBuf<int32_t> qc, qs, qe;
-    DBuf<uint8_t> qout;
+    DeviceBuffer<int32_t> is, ie;
+    DeviceBuffer<int64_t> chrom_off;
+    DeviceBuffer<int32_t> qc, qs, qe;
+    DeviceBuffer<uint8_t> qout;
 };
 
 extern "C" {
@@ -265,18 +240,18 @@ static int est_build(est_catalog* cat, const int32_t* chrom, const int32_t* star
 {
     hipStream_t st = cat->st;
     const int n_chrom = cat->n_chrom;
-    DBuf<int32_t> d_chrom, d_start, d_end, end_sorted;
-    DBuf<unsigned long long> key, key_sorted;
-    DBuf<SegMax> scan_in, scan_out;
-    DBuf<uint32_t> cnt, off;
-    DBuf<uint8_t> eff, tmp;
+    DeviceBuffer<int32_t> d_chrom, d_start, d_end, end_sorted;
+    DeviceBuffer<unsigned long long> key, key_sorted;
+    DeviceBuffer<SegMax> scan_in, scan_out;
+    DeviceBuffer<uint32_t> cnt, off;
+    DeviceBuffer<uint8_t> eff, tmp;
     EST_HIP(hipEventRecord(cat->ev[0], st));
     EST_HIP(cat->chrom_off.reserve((size_t)n_chrom + 1));
     if (n == 0) {
         EST_HIP(hipMemsetAsync(cat->chrom_off.p, 0, ((size_t)n_chrom + 1) * sizeof(int64_t), st));
         EST_HIP(hipEventRecord(cat->ev[1], st));
         EST_HIP(hipStreamSynchronize(st));
-        (void)hipEventElapsedTime(&cat->build_ms, cat->ev[0], cat->ev[1]);
+        cat->build_ms = hiphost::elapsed(cat->ev[0], cat->ev[1]);
         return DSA_OK;
     }
     EST_HIP(d_chrom.reserve((size_t)n));
@@ -298,32 +273,26 @@ static int est_build(est_catalog* cat, const int32_t* chrom, const int32_t* star
     int chrom_bits = 0;
     while (chrom_bits < 31 && ((int64_t)1 << chrom_bits) < n_chrom) ++chrom_bits;
     // stable: equal keys keep the input order, the canonical order of degenerate ties
-    size_t tb = 0;
-    EST_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key.p, key_sorted.p, d_end.p, end_sorted.p, ni, 0, 32 + chrom_bits, st));
-    EST_HIP(tmp.reserve(tb));
-    tb = tmp.cap;
-    EST_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, key.p, key_sorted.p, d_end.p, end_sorted.p, ni, 0, 32 + chrom_bits, st));
+    EST_HIP(hiphost::cub_run(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceRadixSort::SortPairs(t, tb, key.p, key_sorted.p, d_end.p, end_sorted.p, ni, 0, 32 + chrom_bits, st);
+    }));
     const unsigned long long* K = key_sorted.p;
     const int32_t* E = end_sorted.p;
     if (cat->n_degenerate) {
         EST_HIP(eff.reserve((size_t)n));
         EST_HIP(hipMemsetAsync(eff.p, 0, (size_t)n, st));
         hipLaunchKernelGGL(k_est_p_in, dim3(g), dim3(BLOCK), 0, st, K, E, scan_in.p, n);
-        tb = 0;
-        EST_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, scan_in.p, scan_out.p, SegMaxOp(), ni, st));
-        EST_HIP(tmp.reserve(tb));
-        tb = tmp.cap;
-        EST_HIP(hipcub::DeviceScan::InclusiveScan(tmp.p, tb, scan_in.p, scan_out.p, SegMaxOp(), ni, st));
+        EST_HIP(hiphost::cub_run(tmp, [&](void* t, size_t& tb) {
+            return hipcub::DeviceScan::InclusiveScan(t, tb, scan_in.p, scan_out.p, SegMaxOp(), ni, st);
+        }));
         hipLaunchKernelGGL(k_est_deg_flag, dim3(g1), dim3(BLOCK), 0, st, K, E, cnt.p, n);
-        tb = 0;
-        EST_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt.p, off.p, ni + 1, st));
-        EST_HIP(tmp.reserve(tb));
-        tb = tmp.cap;
-        EST_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, cnt.p, off.p, ni + 1, st));
+        EST_HIP(hiphost::cub_run(tmp, [&](void* t, size_t& tb) {
+            return hipcub::DeviceScan::ExclusiveSum(t, tb, cnt.p, off.p, ni + 1, st);
+        }));
         const int64_t nd = cat->n_degenerate;
-        DBuf<uint32_t> d_row;
-        DBuf<int32_t> dc, ds;
-        DBuf<long long> dp;
+        DeviceBuffer<uint32_t> d_row;
+        DeviceBuffer<int32_t> dc, ds;
+        DeviceBuffer<long long> dp;
         EST_HIP(d_row.reserve((size_t)nd));
         EST_HIP(dc.reserve((size_t)nd));
         EST_HIP(ds.reserve((size_t)nd));
@@ -338,17 +307,13 @@ static int est_build(est_catalog* cat, const int32_t* chrom, const int32_t* star
     }
     const uint8_t* EF = cat->n_degenerate ? eff.p : nullptr;
     hipLaunchKernelGGL(k_est_m_in, dim3(g), dim3(BLOCK), 0, st, K, E, EF, scan_in.p, n);
-    tb = 0;
-    EST_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, scan_in.p, scan_out.p, SegMaxOp(), ni, st));
-    EST_HIP(tmp.reserve(tb));
-    tb = tmp.cap;
-    EST_HIP(hipcub::DeviceScan::InclusiveScan(tmp.p, tb, scan_in.p, scan_out.p, SegMaxOp(), ni, st));
+    EST_HIP(hiphost::cub_run(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceScan::InclusiveScan(t, tb, scan_in.p, scan_out.p, SegMaxOp(), ni, st);
+    }));
     hipLaunchKernelGGL(k_est_mark, dim3(g1), dim3(BLOCK), 0, st, K, E, EF, scan_in.p, scan_out.p, cnt.p, n);
-    tb = 0;
-    EST_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt.p, off.p, ni + 1, st));
-    EST_HIP(tmp.reserve(tb));
-    tb = tmp.cap;
-    EST_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, cnt.p, off.p, ni + 1, st));
+    EST_HIP(hiphost::cub_run(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tb, cnt.p, off.p, ni + 1, st);
+    }));
     uint32_t n_islands = 0;
     EST_HIP(hipMemcpyAsync(&n_islands, off.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     EST_HIP(hipStreamSynchronize(st));
@@ -361,7 +326,7 @@ static int est_build(est_catalog* cat, const int32_t* chrom, const int32_t* star
     EST_HIP(hipStreamSynchronize(st));
     EST_HIP(hipGetLastError());
     cat->n_islands = n_islands;
-    (void)hipEventElapsedTime(&cat->build_ms, cat->ev[0], cat->ev[1]);
+    cat->build_ms = hiphost::elapsed(cat->ev[0], cat->ev[1]);
     return DSA_OK;
 }
 
@@ -378,8 +343,7 @@ int est_catalog_create(int device, const int32_t* chrom, const int32_t* start, c
         if (chrom[k] < 0 || chrom[k] >= n_chrom) { g_est_err = "chromosome id out of range at segment " + std::to_string(k); return DSA_E_ARG; }
         n_deg += end[k] < start[k];
     }
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || device < 0 || device >= nd) { g_est_err = "no usable HIP device"; return DSA_E_DEVICE; }
+    if (hiphost::check_device(device, &g_est_err)) return DSA_E_DEVICE;
     EST_HIP(hipSetDevice(device));
     est_catalog* cat = new est_catalog();
     cat->device = device;
@@ -437,7 +401,7 @@ int est_catalog_contained(est_catalog* cat, const int32_t* chrom, const int32_t*
         EST_HIP(hipEventRecord(cat->ev[1], st));
         EST_HIP(hipStreamSynchronize(st));
         EST_HIP(hipGetLastError());
-        (void)hipEventElapsedTime(&ms, cat->ev[0], cat->ev[1]);
+        ms = hiphost::elapsed(cat->ev[0], cat->ev[1]);
     }
     if (timing) {
         int64_t hit = 0;

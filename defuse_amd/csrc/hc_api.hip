@@ -10,31 +10,24 @@
 // computes it.  Latency/HBM bound integer-and-compare work; nothing here is a contraction.
 #include <hip/hip_runtime.h>
 
-#include "hip_raii.hpp"
+#include "hip_host.hpp"
 
 #include <chrono>
-#include <cstdio>
 #include <string>
 #include <vector>
 
+#include "../../include/defuse_dsa.h"
 #include "../../include/defuse_hc.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-std::string g_err;
+using hiphost::DeviceBuffer;
 
-#define HC_HIP(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            char b_[256];                                                                         \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            g_err = b_;                                                                           \
-            return -2;                                                                            \
-        }                                                                                         \
-    } while (0)
+thread_local std::string g_err;
+
+#define HC_HIP(call) HIPHOST_TRY(g_err, call)
 
 struct HcTable {
     int64_t in_off;      // into the caller's distances
@@ -181,13 +174,6 @@ __global__ __launch_bounds__(HC_THREADS) void k_hc(const HcTable* __restrict__ t
     if (tid == 0) { n_clusters[blockIdx.x] = m; n_merges[blockIdx.x] = merges; }
 }
 
-template <class T>
-struct DevMem {
-    T* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
-};
-
 double now_ms()
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -207,12 +193,8 @@ extern "C" int hc_cluster_batch(int device, int32_t n_tables, const int32_t* n_i
         g_err = "hc_cluster_batch: null argument";
         return -1;
     }
-    if (n_tables == 0) return 0;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        g_err = "hc_cluster_batch: no such HIP device";
-        return -2;
-    }
+    if (n_tables == 0) return DSA_OK;
+    if (hiphost::check_device(device, &g_err)) return DSA_E_DEVICE;
     HC_HIP(hipSetDevice(device));
 
     std::vector<HcTable> tabs(n_tables);
@@ -232,16 +214,16 @@ extern "C" int hc_cluster_batch(int device, int32_t n_tables, const int32_t* n_i
         return -1;
     }
 
-    DevMem<HcTable> d_tabs; DevMem<double> d_in, d_D; DevMem<uint32_t> d_S;
-    DevMem<int32_t> d_slots, d_members, d_cluster_of, d_ncl, d_nmerge;
-    HC_HIP(d_tabs.alloc(n_tables)); HC_HIP(d_in.alloc(in_end)); HC_HIP(d_D.alloc(mat)); HC_HIP(d_S.alloc(mat));
-    HC_HIP(d_slots.alloc(slots)); HC_HIP(d_members.alloc(items)); HC_HIP(d_cluster_of.alloc(items));
-    HC_HIP(d_ncl.alloc(n_tables)); HC_HIP(d_nmerge.alloc(n_tables));
+    DeviceBuffer<HcTable> d_tabs; DeviceBuffer<double> d_in, d_D; DeviceBuffer<uint32_t> d_S;
+    DeviceBuffer<int32_t> d_slots, d_members, d_cluster_of, d_ncl, d_nmerge;
+    HC_HIP(d_tabs.reserve(n_tables)); HC_HIP(d_in.reserve(in_end)); HC_HIP(d_D.reserve(mat)); HC_HIP(d_S.reserve(mat));
+    HC_HIP(d_slots.reserve(slots)); HC_HIP(d_members.reserve(items)); HC_HIP(d_cluster_of.reserve(items));
+    HC_HIP(d_ncl.reserve(n_tables)); HC_HIP(d_nmerge.reserve(n_tables));
     HC_HIP(hipMemcpy(d_tabs.p, tabs.data(), sizeof(HcTable) * n_tables, hipMemcpyHostToDevice));
     if (in_end) HC_HIP(hipMemcpy(d_in.p, distances, sizeof(double) * in_end, hipMemcpyHostToDevice));
     const double t_up = now_ms();
 
-    hipraii::Event e0, e1;                 // destroyed on every return
+    hiphost::Event e0, e1;                 // destroyed on every return
     HC_HIP(e0.create()); HC_HIP(e1.create());
     HC_HIP(hipEventRecord(e0, nullptr));
     hipLaunchKernelGGL(k_hc, dim3(n_tables), dim3(HC_THREADS), 0, nullptr, d_tabs.p, d_in.p, d_D.p, d_S.p, d_slots.p,
@@ -267,5 +249,5 @@ extern "C" int hc_cluster_batch(int device, int32_t n_tables, const int32_t* n_i
         timing->total_ms = (float)(now_ms() - t_begin);
         timing->n_merges = (int32_t)tot;
     }
-    return 0;
+    return DSA_OK;
 }

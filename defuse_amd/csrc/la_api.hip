@@ -24,11 +24,10 @@
 // 40-byte descriptor per pair (k_pack_win).  Both run the same launch groups and the same two kernels.
 #include <hip/hip_runtime.h>
 
-#include "hip_raii.hpp"
+#include "hip_host.hpp"
 
 #include <algorithm>
 #include <chrono>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -345,7 +344,7 @@ __global__ __launch_bounds__(WG_WAVES * WAVE) void k_la32(const Lane* __restrict
 
 struct la_genome {             // include/defuse_la.h: the contig bytes of a genome in HBM
     int device;
-    uint8_t* bytes;
+    hiphost::DeviceBuffer<uint8_t> bytes;
     int64_t len;
 };
 
@@ -353,29 +352,12 @@ namespace {
 
 using namespace la;
 
-thread_local std::string g_err;
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIPL(call)                                                                                    \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return fail(DSA_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_));      \
-    } while (0)
+using hiphost::DeviceBuffer;
+using hiphost::fail;
 
-template <class T>
-struct Buf {
-    T* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
+thread_local std::string g_err;
+
+#define HIPL(call) HIPHOST_TRY(g_err, call)
 
 // One launch group: the waves built from `order[begin..end)`, ITEMS pairs per lane.
 struct Group {
@@ -462,15 +444,15 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
     tm.n_int32 = (int32_t)first16;
     tm.n_packed16 = (int32_t)(n_items - first16);
 
-    Buf<uint8_t> d_pool;
-    Buf<Item> d_items;
-    Buf<int32_t> d_scores;
-    HIPL(d_pool.alloc((size_t)pool_len));
-    HIPL(d_items.alloc((size_t)n_items));
-    HIPL(d_scores.alloc((size_t)n_items));
+    DeviceBuffer<uint8_t> d_pool;
+    DeviceBuffer<Item> d_items;
+    DeviceBuffer<int32_t> d_scores;
+    HIPL(d_pool.reserve((size_t)pool_len));
+    HIPL(d_items.reserve((size_t)n_items));
+    HIPL(d_scores.reserve((size_t)n_items));
     if (pool_len > 0) HIPL(hipMemcpy(d_pool.p, pool, (size_t)pool_len, hipMemcpyHostToDevice));
     HIPL(hipMemcpy(d_items.p, items, (size_t)n_items * sizeof(Item), hipMemcpyHostToDevice));
-    hipraii::Event ev[3];                 // destroyed on every return
+    hiphost::Event ev[3];                 // destroyed on every return
     for (auto& e : ev) HIPL(e.create());
 
     size_t budget_dwords = (size_t)2 << 28;       // 2 GiB of planes per launch group
@@ -487,21 +469,21 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
                 k += n;
                 if ((size_t)(g.ref_dwords + g.row_dwords + g.bnd_dwords) >= budget_dwords) break;
             }
-            Buf<Lane> d_lanes;
-            Buf<Wave> d_waves;
-            Buf<uint32_t> d_ref, d_row, d_bnd;
-            HIPL(d_lanes.alloc(g.lanes.size()));
-            HIPL(d_waves.alloc(g.waves.size()));
-            HIPL(d_ref.alloc((size_t)g.ref_dwords));
-            HIPL(d_row.alloc((size_t)g.row_dwords));
-            HIPL(d_bnd.alloc((size_t)g.bnd_dwords));
+            DeviceBuffer<Lane> d_lanes;
+            DeviceBuffer<Wave> d_waves;
+            DeviceBuffer<uint32_t> d_ref, d_row, d_bnd;
+            HIPL(d_lanes.reserve(g.lanes.size()));
+            HIPL(d_waves.reserve(g.waves.size()));
+            HIPL(d_ref.reserve((size_t)g.ref_dwords));
+            HIPL(d_row.reserve((size_t)g.row_dwords));
+            HIPL(d_bnd.reserve((size_t)g.bnd_dwords));
             HIPL(hipMemcpy(d_lanes.p, g.lanes.data(), g.lanes.size() * sizeof(Lane), hipMemcpyHostToDevice));
             HIPL(hipMemcpy(d_waves.p, g.waves.data(), g.waves.size() * sizeof(Wave), hipMemcpyHostToDevice));
             const int n_waves = (int)g.waves.size();
             HIPL(hipEventRecord(ev[0], nullptr));
             pack(items_per_lane, n_waves, d_pool.p, d_items.p, d_lanes.p, d_waves.p, d_ref.p, d_row.p);
             HIPL(hipEventRecord(ev[1], nullptr));
-            const unsigned grid = (unsigned)((n_waves + WG_WAVES - 1) / WG_WAVES);
+            const unsigned grid = hiphost::grid_of(n_waves, WG_WAVES);
             if (items_per_lane == 2)
                 hipLaunchKernelGGL(k_la16, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
                                    d_bnd.p, prm, d_scores.p);
@@ -543,13 +525,13 @@ int la_align_batch_min(int device, int32_t match, int32_t mismatch, int32_t gap,
 {
     const auto t_begin = std::chrono::steady_clock::now();
     la_timing tm{};
-    if (n_items < 0 || (n_items > 0 && (!items || !scores || !pool))) return fail(DSA_E_ARG, "null argument");
-    if (n_items >= (int64_t)1 << 31) return fail(DSA_E_LIMIT, "more than 2^31-1 pairs");
+    if (n_items < 0 || (n_items > 0 && (!items || !scores || !pool))) return fail(g_err, DSA_E_ARG, "null argument");
+    if (n_items >= (int64_t)1 << 31) return fail(g_err, DSA_E_LIMIT, "more than 2^31-1 pairs");
     for (int64_t k = 0; k < n_items; ++k) {
         const la_item& it = items[k];
         if (it.ref_len < 0 || it.seq_len < 0 || it.ref_off < 0 || it.seq_off < 0 || it.ref_off + it.ref_len > pool_len ||
             it.seq_off + it.seq_len > pool_len)
-            return fail(DSA_E_ARG, "pair %lld lies outside the pool", (long long)k);
+            return fail(g_err, DSA_E_ARG, "pair %lld lies outside the pool", (long long)k);
         tm.cells += ((int64_t)it.ref_len + 1) * ((int64_t)it.seq_len + 1);
     }
     if (n_items == 0) {
@@ -572,19 +554,17 @@ int la_align_batch_min(int device, int32_t match, int32_t mismatch, int32_t gap,
 
 int la_genome_create(int device, const uint8_t* bytes, int64_t len, la_genome** out)
 {
-    if (!out || len < 0 || (len > 0 && !bytes)) return fail(DSA_E_ARG, "null argument");
+    if (!out || len < 0 || (len > 0 && !bytes)) return fail(g_err, DSA_E_ARG, "null argument");
     *out = nullptr;
     HIPL(hipSetDevice(device));
-    uint8_t* d = nullptr;
-    HIPL(hipMalloc((void**)&d, (size_t)std::max<int64_t>(len, 1)));
+    DeviceBuffer<uint8_t> d;           // freed on the early returns
+    HIPL(d.reserve((size_t)len));
     if (len > 0) {
-        const hipError_t e = hipMemcpy(d, bytes, (size_t)len, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return fail(DSA_E_DEVICE, "hipMemcpy of the genome: %s", hipGetErrorString(e));
-        }
+        const hipError_t e = hipMemcpy(d.p, bytes, (size_t)len, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(g_err, DSA_E_DEVICE, "hipMemcpy of the genome: %s", hipGetErrorString(e));
     }
-    *out = new la_genome{device, d, len};
+    *out = new la_genome{device, {}, len};
+    (*out)->bytes.swap(d);
     return DSA_OK;
 }
 
@@ -592,7 +572,6 @@ void la_genome_destroy(la_genome* genome)
 {
     if (!genome) return;
     (void)hipSetDevice(genome->device);
-    (void)hipFree(genome->bytes);
     delete genome;
 }
 
@@ -601,19 +580,19 @@ int la_align_windows_min(const la_genome* genome, int32_t match, int32_t mismatc
 {
     const auto t_begin = std::chrono::steady_clock::now();
     la_timing tm{};
-    if (!genome || n_windows < 0 || (n_windows > 0 && (!windows || !scores || (!pool && pool_len > 0)))) return fail(DSA_E_ARG, "null argument");
-    if (n_windows >= (int64_t)1 << 31) return fail(DSA_E_LIMIT, "more than 2^31-1 pairs");
+    if (!genome || n_windows < 0 || (n_windows > 0 && (!windows || !scores || (!pool && pool_len > 0)))) return fail(g_err, DSA_E_ARG, "null argument");
+    if (n_windows >= (int64_t)1 << 31) return fail(g_err, DSA_E_LIMIT, "more than 2^31-1 pairs");
     for (int64_t k = 0; k < n_windows; ++k) {
         const la_window& wd = windows[k];
         const int64_t lr = (int64_t)wd.pad_left + wd.slice_len + wd.pad_right;
         if (wd.slice_off < 0 || wd.slice_len < 0 || wd.pad_left < 0 || wd.pad_right < 0 || wd.slice_off + wd.slice_len > genome->len ||
             lr > INT32_MAX)
-            return fail(DSA_E_ARG, "window %lld lies outside the genome", (long long)k);
+            return fail(g_err, DSA_E_ARG, "window %lld lies outside the genome", (long long)k);
         if (wd.seq_len < 0 || wd.seq_off < 0 || wd.seq_off + wd.seq_len > pool_len)
-            return fail(DSA_E_ARG, "sequence %lld lies outside the pool", (long long)k);
+            return fail(g_err, DSA_E_ARG, "sequence %lld lies outside the pool", (long long)k);
         tm.cells += (lr + 1) * ((int64_t)wd.seq_len + 1);
     }
-    const uint8_t* d_genome = genome->bytes;
+    const uint8_t* d_genome = genome->bytes.p;
     const int rc = align_items(genome->device, match, mismatch, gap, pool, pool_len, windows, n_windows, min_score, scores, tm,
                                [d_genome](int items_per_lane, int n_waves, const uint8_t* d_pool, const la_window* d_wins, const Lane* d_lanes,
                                           const Wave* d_waves, uint32_t* d_ref, uint32_t* d_row) {

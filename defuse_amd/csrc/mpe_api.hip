@@ -14,7 +14,7 @@
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
-#include "hip_raii.hpp"
+#include "hip_host.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -23,23 +23,17 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/defuse_dsa.h"
 #include "../../include/defuse_mpe.h"
 
 namespace {
 
+using hiphost::DeviceBuffer;
+
 thread_local std::string g_mpe_err;     // per host thread: the sharded call runs one per device
 std::string g_mpe_err_sharded;
 
-#define MPE_HIP(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            char b_[256];                                                                         \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            g_mpe_err = b_;                                                                       \
-            return -2;                                                                            \
-        }                                                                                         \
-    } while (0)
+#define MPE_HIP(call) HIPHOST_TRY(g_mpe_err, call)
 
 constexpr double R8_HUGE = 1.0e30;          // tools/asa136.C r8_huge
 constexpr double DBL_MAX_ = 1.7976931348623157e308;
@@ -1383,13 +1377,6 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(MPE_WPE, MPE
     if (lane == 0) atomicAdd(iters, (unsigned long long)my_iters);
 }
 
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 extern "C" const char* mpe_last_error(void) { return g_mpe_err.empty() ? g_mpe_err_sharded.c_str() : g_mpe_err.c_str(); }
@@ -1400,26 +1387,25 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
                                  mpe_timing* timing)
 {
     mpe_timing t{};
-    if (!params || n_problems < 0 || (n_problems && !prob_off)) { g_mpe_err = "bad arguments"; return -3; }
+    if (!params || n_problems < 0 || (n_problems && !prob_off)) { g_mpe_err = "bad arguments"; return DSA_E_ARG; }
     const int64_t n_mp = n_problems ? prob_off[n_problems] : 0;
     t.n_problems = n_problems;
     t.n_mate_pairs = n_mp;
-    if (n_problems == 0) { if (timing) *timing = t; return 0; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_mpe_err = "no usable HIP device"; return -2; }
+    if (n_problems == 0) { if (timing) *timing = t; return DSA_OK; }
+    if (hiphost::check_device(device, &g_mpe_err)) return DSA_E_DEVICE;
     MPE_HIP(hipSetDevice(device));
     for (int p = 0; p < n_problems; ++p) {
         const int64_t n = prob_off[p + 1] - prob_off[p];
-        if (n < 0 || n > 0x7FFFFFF) { g_mpe_err = "problem too large"; return -4; }
+        if (n < 0 || n > 0x7FFFFFF) { g_mpe_err = "problem too large"; return DSA_E_LIMIT; }
     }
-    DBuf<int64_t> d_off;
-    DBuf<double> d_x, d_y, d_u;
-    DBuf<int32_t> d_txo, d_tyo, d_nc, d_status;
-    DBuf<uint16_t> d_member;
-    DBuf<unsigned long long> d_iters;
-    MPE_HIP(d_off.alloc(n_problems + 1));
-    MPE_HIP(d_x.alloc(n_mp)); MPE_HIP(d_y.alloc(n_mp)); MPE_HIP(d_u.alloc(n_mp)); MPE_HIP(d_txo.alloc(n_mp)); MPE_HIP(d_tyo.alloc(n_mp));
-    MPE_HIP(d_nc.alloc(n_problems)); MPE_HIP(d_status.alloc(n_problems)); MPE_HIP(d_member.alloc(n_mp)); MPE_HIP(d_iters.alloc(1));
+    DeviceBuffer<int64_t> d_off;
+    DeviceBuffer<double> d_x, d_y, d_u;
+    DeviceBuffer<int32_t> d_txo, d_tyo, d_nc, d_status;
+    DeviceBuffer<uint16_t> d_member;
+    DeviceBuffer<unsigned long long> d_iters;
+    MPE_HIP(d_off.reserve(n_problems + 1));
+    MPE_HIP(d_x.reserve(n_mp)); MPE_HIP(d_y.reserve(n_mp)); MPE_HIP(d_u.reserve(n_mp)); MPE_HIP(d_txo.reserve(n_mp)); MPE_HIP(d_tyo.reserve(n_mp));
+    MPE_HIP(d_nc.reserve(n_problems)); MPE_HIP(d_status.reserve(n_problems)); MPE_HIP(d_member.reserve(n_mp)); MPE_HIP(d_iters.reserve(1));
     MPE_HIP(hipMemcpy(d_off.p, prob_off, (n_problems + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (n_mp) {
         MPE_HIP(hipMemcpy(d_x.p, x, n_mp * sizeof(double), hipMemcpyHostToDevice));
@@ -1432,21 +1418,21 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
     // DEFUSE_MPE_DUMP_ITERS=<file>: per problem twelve int64 — [0] the chosen K, [K] the EM iterations of the fit with K
     // components, [11] those of the refit — for the problems a wave fits (tests compare them with the restatement's)
     const char* dump_iters = getenv("DEFUSE_MPE_DUMP_ITERS");
-    DBuf<long long> d_by_k;
-    DBuf<double> d_ll_by_k;                  // ... followed in the file by twelve doubles per problem: [K] the log-likelihood fit K ended with
+    DeviceBuffer<long long> d_by_k;
+    DeviceBuffer<double> d_ll_by_k;                  // ... followed in the file by twelve doubles per problem: [K] the log-likelihood fit K ended with
     if (dump_iters) {
-        MPE_HIP(d_by_k.alloc((size_t)n_problems * 12));
+        MPE_HIP(d_by_k.reserve((size_t)n_problems * 12));
         MPE_HIP(hipMemset(d_by_k.p, 0, (size_t)n_problems * 12 * sizeof(long long)));
-        MPE_HIP(d_ll_by_k.alloc((size_t)n_problems * 12));
+        MPE_HIP(d_ll_by_k.reserve((size_t)n_problems * 12));
         MPE_HIP(hipMemset(d_ll_by_k.p, 0, (size_t)n_problems * 12 * sizeof(double)));
     }
-    hipraii::Event e0, e1, e2;               // destroyed on every return, the early ones of MPE_HIP included
+    hiphost::Event e0, e1, e2;               // destroyed on every return, the early ones of MPE_HIP included
     MPE_HIP(e0.create());
     MPE_HIP(e1.create());
     MPE_HIP(e2.create());
     constexpr size_t MAX_SHARES = 4;
-    hipraii::Stream s_wave, s_share[MAX_SHARES - 1];
-    hipraii::Event e_seed, e_share[MAX_SHARES - 1];
+    hiphost::Stream s_wave, s_share[MAX_SHARES - 1];
+    hiphost::Event e_seed, e_share[MAX_SHARES - 1];
     MPE_HIP(s_wave.create(hipStreamNonBlocking));
     MPE_HIP(e_seed.create());
     for (size_t k = 0; k + 1 < MAX_SHARES; ++k) {
@@ -1498,17 +1484,17 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
             return prob_off[p0 + a + 1] - prob_off[p0 + a] > prob_off[p0 + b + 1] - prob_off[p0 + b];
         });
-        DBuf<int64_t> d_wd, d_wi;
-        DBuf<ProblemSeeds> d_seeds;
-        DBuf<int> d_km_ifault;
-        DBuf<int64_t> d_km_off;
-        DBuf<double> d_km_scratch;
-        DBuf<int32_t> d_order, d_state;
-        DBuf<double> d_work, d_bic;
-        DBuf<int> d_iwork;
-        MPE_HIP(d_wd.alloc(wd.size())); MPE_HIP(d_wi.alloc(wi.size())); MPE_HIP(d_order.alloc(order.size()));
-        MPE_HIP(d_state.alloc((size_t)n_chunk * MPE_KMAX)); MPE_HIP(d_bic.alloc((size_t)n_chunk * MPE_KMAX));
-        MPE_HIP(d_work.alloc((size_t)wd.back())); MPE_HIP(d_iwork.alloc((size_t)wi.back()));
+        DeviceBuffer<int64_t> d_wd, d_wi;
+        DeviceBuffer<ProblemSeeds> d_seeds;
+        DeviceBuffer<int> d_km_ifault;
+        DeviceBuffer<int64_t> d_km_off;
+        DeviceBuffer<double> d_km_scratch;
+        DeviceBuffer<int32_t> d_order, d_state;
+        DeviceBuffer<double> d_work, d_bic;
+        DeviceBuffer<int> d_iwork;
+        MPE_HIP(d_wd.reserve(wd.size())); MPE_HIP(d_wi.reserve(wi.size())); MPE_HIP(d_order.reserve(order.size()));
+        MPE_HIP(d_state.reserve((size_t)n_chunk * MPE_KMAX)); MPE_HIP(d_bic.reserve((size_t)n_chunk * MPE_KMAX));
+        MPE_HIP(d_work.reserve((size_t)wd.back())); MPE_HIP(d_iwork.reserve((size_t)wi.back()));
         MPE_HIP(hipMemcpy(d_wd.p, wd.data(), wd.size() * sizeof(int64_t), hipMemcpyHostToDevice));
         MPE_HIP(hipMemcpy(d_wi.p, wi.data(), wi.size() * sizeof(int64_t), hipMemcpyHostToDevice));
         MPE_HIP(hipMemcpy(d_order.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1521,8 +1507,8 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
         MPE_HIP(hipEventRecord(e0, 0));
         MPE_HIP(hipStreamWaitEvent(s_wave, e0, 0));
         if (n_large) {               // order[0 .. n_large): the problems with a wave of their own, largest first
-            MPE_HIP(d_seeds.alloc((size_t)n_large));
-            MPE_HIP(d_km_ifault.alloc((size_t)n_large * (MPE_KMAX + 1)));
+            MPE_HIP(d_seeds.reserve((size_t)n_large));
+            MPE_HIP(d_km_ifault.reserve((size_t)n_large * (MPE_KMAX + 1)));
             // scratch slabs of the k-means blocks: group gi (64 problems of neighbouring size ranks) needs its largest problem's
             // number of points, for each of the nine K
             const int n_groups = (n_large + WV - 1) / WV;
@@ -1531,9 +1517,9 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
                 const int first = order[(size_t)gi * WV];              // sorted by size: the group's largest
                 km_off[(size_t)gi + 1] = km_off[(size_t)gi] + (prob_off[p0 + first + 1] - prob_off[p0 + first]);
             }
-            MPE_HIP(d_km_off.alloc(km_off.size()));
+            MPE_HIP(d_km_off.reserve(km_off.size()));
             MPE_HIP(hipMemcpy(d_km_off.p, km_off.data(), km_off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-            MPE_HIP(d_km_scratch.alloc((size_t)(MPE_KMAX - 1) * (size_t)km_off.back() * KM_ROW_DOUBLES));
+            MPE_HIP(d_km_scratch.reserve((size_t)(MPE_KMAX - 1) * (size_t)km_off.back() * KM_ROW_DOUBLES));
             hipLaunchKernelGGL(k_mpe_seed, dim3((unsigned)n_large), dim3(WV), 0, s_wave, *params, d_off.p, p0, d_order.p, d_x.p, d_y.p, d_u.p, d_txo.p,
                                d_tyo.p, d_wd.p, d_work.p, d_seeds.p);
             // The k-means kernel ends in a long tail: its longest waves (64 start-ups of the largest problems in lockstep)
@@ -1589,9 +1575,7 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
         MPE_HIP(hipEventRecord(e1, 0));
         MPE_HIP(hipDeviceSynchronize());
         MPE_HIP(hipGetLastError());
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        t.kernel_ms += ms;
+        t.kernel_ms += hiphost::elapsed(e0, e1);
         p0 = p1;
     }
     MPE_HIP(hipMemcpy(n_clusters, d_nc.p, n_problems * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1640,7 +1624,7 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
     }
     for (int p = 0; p < n_problems; ++p) t.n_failed += status[p] != 0;
     if (timing) *timing = t;
-    return 0;
+    return DSA_OK;
 }
 
 extern "C" int mpe_cluster_batch_sharded(const int* devices, int32_t n_devices, const mpe_params* params, const int64_t* prob_off,
@@ -1648,7 +1632,7 @@ extern "C" int mpe_cluster_batch_sharded(const int* devices, int32_t n_devices, 
                                          const int32_t* to_xo, const int32_t* to_yo, int32_t* n_clusters, uint16_t* member,
                                          int32_t* status, mpe_timing* timing)
 {
-    if (!devices || n_devices < 1 || !params || n_problems < 0 || (n_problems && !prob_off)) { g_mpe_err = "bad arguments"; return -3; }
+    if (!devices || n_devices < 1 || !params || n_problems < 0 || (n_problems && !prob_off)) { g_mpe_err = "bad arguments"; return DSA_E_ARG; }
     if (n_devices == 1 || n_problems == 0)
         return mpe_cluster_batch(devices[0], params, prob_off, n_problems, x, y, u, to_xo, to_yo, n_clusters, member, status, timing);
     // contiguous shares of about equal mate pair count
@@ -1688,5 +1672,5 @@ extern "C" int mpe_cluster_batch_sharded(const int* devices, int32_t n_devices, 
         t.n_wave_problems += tm[k].n_wave_problems;
     }
     if (timing) *timing = t;
-    return 0;
+    return DSA_OK;
 }

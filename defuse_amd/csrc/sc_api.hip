@@ -3,30 +3,23 @@
 // per-component greedy is latency-bound; nothing here is shaped into a GEMM.
 #include <hip/hip_runtime.h>
 
-#include "hip_raii.hpp"
+#include "hip_host.hpp"
 #include <hipcub/hipcub.hpp>
 
-#include <cstdio>
 #include <string>
 #include <vector>
 
+#include "../../include/defuse_dsa.h"
 #include "../../include/defuse_sc.h"
 
 namespace {
 
-std::string g_err;
+using hiphost::DeviceBuffer;
+
+thread_local std::string g_err;    // sc_prepare runs on a helper thread beside the caller's sc_cover (tools_src/setcover.cpp)
 constexpr int SMALL_MAX = 32;   // components with more clusters than this get a whole wave
 
-#define SC_HIP(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            char b_[256];                                                                         \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            g_err = b_;                                                                           \
-            return -2;                                                                            \
-        }                                                                                         \
-    } while (0)
+#define SC_HIP(call) HIPHOST_TRY(g_err, call)
 
 // occurrence k of the input -> (element key, owning cluster)
 __global__ void k_occurrences(const int64_t* __restrict__ cluster_off, int32_t n_clusters, int32_t* __restrict__ occ_cluster)
@@ -200,59 +193,49 @@ __global__ void k_collect_large(const int32_t* __restrict__ comp_begin, int32_t 
     if (comp_begin[comp + 1] - comp_begin[comp] > SMALL_MAX) list[atomicAdd(n_large, 1)] = comp;
 }
 
-template <typename T>
-struct Buf {
-    T* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 extern "C" const char* sc_last_error(void) { return g_err.c_str(); }
 
 extern "C" int sc_prepare(int device)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -2;
-    if (hipSetDevice(device) != hipSuccess || hipFree(nullptr) != hipSuccess) return -2;
-    return 0;
+    if (hiphost::check_device(device) || hipSetDevice(device) != hipSuccess || hipFree(nullptr) != hipSuccess) return DSA_E_DEVICE;
+    return DSA_OK;
 }
 
 extern "C" int sc_cover(int device, const int64_t* cluster_off, const int32_t* elements, int32_t n_clusters,
                         int32_t max_element, int32_t* owner, sc_timing* timing)
 {
     sc_timing t{};
-    if (n_clusters < 0 || max_element < -1 || (n_clusters && !cluster_off)) { g_err = "bad arguments"; return -3; }
+    if (n_clusters < 0 || max_element < -1 || (n_clusters && !cluster_off)) { g_err = "bad arguments"; return DSA_E_ARG; }
     const int64_t n_occ = n_clusters ? cluster_off[n_clusters] : 0;
     for (int64_t k = 0; k < n_occ; ++k)
-        if (elements[k] < 0 || elements[k] > max_element) { g_err = "element out of range"; return -3; }
-    if (n_occ >= ((int64_t)1 << 31)) { g_err = "more than 2^31-1 cluster lines"; return -4; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { g_err = "no usable HIP device"; return -2; }
+        if (elements[k] < 0 || elements[k] > max_element) { g_err = "element out of range"; return DSA_E_ARG; }
+    if (n_occ >= ((int64_t)1 << 31)) { g_err = "more than 2^31-1 cluster lines"; return DSA_E_LIMIT; }
+    if (hiphost::check_device(device, &g_err)) return DSA_E_DEVICE;
     SC_HIP(hipSetDevice(device));
     for (int64_t e = 0; e <= max_element; ++e) owner[e] = -1;
-    if (n_clusters == 0 || n_occ == 0) { if (timing) *timing = t; return 0; }
+    if (n_clusters == 0 || n_occ == 0) { if (timing) *timing = t; return DSA_OK; }
 
-    hipraii::Event ev[4];                 // destroyed on every return
+    hiphost::Event ev[4];                 // destroyed on every return
     for (auto& e : ev) SC_HIP(e.create());
-    Buf<int64_t> d_coff, d_e2c_off;
-    Buf<int32_t> d_el, d_occ_cluster, d_keys_sorted, d_e2c, d_label, d_label_sorted, d_idx, d_comp_clusters, d_flag, d_rank,
+    DeviceBuffer<int64_t> d_coff, d_e2c_off;
+    DeviceBuffer<int32_t> d_el, d_occ_cluster, d_keys_sorted, d_e2c, d_label, d_label_sorted, d_idx, d_comp_clusters, d_flag, d_rank,
         d_comp_begin, d_size, d_seq, d_owner, d_large, d_nlarge;
-    Buf<int> d_changed;
-    Buf<uint8_t> d_tmp;
+    DeviceBuffer<int> d_changed;
+    DeviceBuffer<uint8_t> d_tmp;
     const int nel = max_element + 1;
-    SC_HIP(d_coff.alloc(n_clusters + 1)); SC_HIP(d_el.alloc(n_occ)); SC_HIP(d_occ_cluster.alloc(n_occ));
-    SC_HIP(d_keys_sorted.alloc(n_occ)); SC_HIP(d_e2c.alloc(n_occ)); SC_HIP(d_e2c_off.alloc(nel + 2));
-    SC_HIP(d_label.alloc(n_clusters)); SC_HIP(d_label_sorted.alloc(n_clusters)); SC_HIP(d_idx.alloc(n_clusters));
-    SC_HIP(d_comp_clusters.alloc(n_clusters)); SC_HIP(d_flag.alloc(n_clusters)); SC_HIP(d_rank.alloc(n_clusters));
-    SC_HIP(d_comp_begin.alloc(n_clusters + 2)); SC_HIP(d_size.alloc(n_clusters)); SC_HIP(d_seq.alloc(n_clusters));
-    SC_HIP(d_owner.alloc(nel)); SC_HIP(d_large.alloc(n_clusters)); SC_HIP(d_nlarge.alloc(1)); SC_HIP(d_changed.alloc(1));
+    SC_HIP(d_coff.reserve(n_clusters + 1)); SC_HIP(d_el.reserve(n_occ)); SC_HIP(d_occ_cluster.reserve(n_occ));
+    SC_HIP(d_keys_sorted.reserve(n_occ)); SC_HIP(d_e2c.reserve(n_occ)); SC_HIP(d_e2c_off.reserve(nel + 2));
+    SC_HIP(d_label.reserve(n_clusters)); SC_HIP(d_label_sorted.reserve(n_clusters)); SC_HIP(d_idx.reserve(n_clusters));
+    SC_HIP(d_comp_clusters.reserve(n_clusters)); SC_HIP(d_flag.reserve(n_clusters)); SC_HIP(d_rank.reserve(n_clusters));
+    SC_HIP(d_comp_begin.reserve(n_clusters + 2)); SC_HIP(d_size.reserve(n_clusters)); SC_HIP(d_seq.reserve(n_clusters));
+    SC_HIP(d_owner.reserve(nel)); SC_HIP(d_large.reserve(n_clusters)); SC_HIP(d_nlarge.reserve(1)); SC_HIP(d_changed.reserve(1));
     SC_HIP(hipMemcpy(d_coff.p, cluster_off, (n_clusters + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     SC_HIP(hipMemcpy(d_el.p, elements, n_occ * sizeof(int32_t), hipMemcpyHostToDevice));
     SC_HIP(hipMemset(d_owner.p, 0xFF, nel * sizeof(int32_t)));
     const int B = 256;
-    auto grid = [&](int64_t n) { return dim3((unsigned)((n + B - 1) / B)); };
+    auto grid = [&](int64_t n) { return dim3(hiphost::grid_of(n, B)); };
 
     // 1. fragment -> clusters index: stable radix sort of the occurrences by fragment keeps each list in
     //    ascending cluster order (the order tools/setcover.cpp:47-60 builds it in)
@@ -269,7 +252,7 @@ extern "C" int sc_cover(int device, const int64_t* cluster_off, const int32_t* e
     tmp_bytes = std::max(tmp_bytes, need);
     SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_flag.p, d_rank.p, n_clusters));
     tmp_bytes = std::max(tmp_bytes, need);
-    SC_HIP(d_tmp.alloc(tmp_bytes));
+    SC_HIP(d_tmp.reserve(tmp_bytes));
     need = tmp_bytes;
     SC_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_el.p, d_keys_sorted.p, d_occ_cluster.p, d_e2c.p, (int)n_occ, 0, bits));
     hipLaunchKernelGGL(k_lower_bounds, grid(nel + 1), dim3(B), 0, 0, d_keys_sorted.p, n_occ, max_element, d_e2c_off.p);
@@ -286,7 +269,7 @@ extern "C" int sc_cover(int device, const int64_t* cluster_off, const int32_t* e
         SC_HIP(hipMemcpy(&changed, d_changed.p, sizeof(int), hipMemcpyDeviceToHost));
         ++iterations;
         if (!changed) break;
-        if (iterations > 10000) { g_err = "connected components did not converge"; return -2; }
+        if (iterations > 10000) { g_err = "connected components did not converge"; return DSA_E_DEVICE; }
     }
     // clusters grouped by component, ascending index inside a component (stable sort by label)
     hipLaunchKernelGGL(k_iota, grid(n_clusters), dim3(B), 0, 0, d_idx.p, n_clusters);
@@ -315,13 +298,13 @@ extern "C" int sc_cover(int device, const int64_t* cluster_off, const int32_t* e
     SC_HIP(hipDeviceSynchronize());
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpy(owner, d_owner.p, nel * sizeof(int32_t), hipMemcpyDeviceToHost));
-    (void)hipEventElapsedTime(&t.build_ms, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&t.components_ms, ev[1], ev[2]);
-    (void)hipEventElapsedTime(&t.greedy_ms, ev[2], ev[3]);
-    (void)hipEventElapsedTime(&t.total_ms, ev[0], ev[3]);
+    t.build_ms = hiphost::elapsed(ev[0], ev[1]);
+    t.components_ms = hiphost::elapsed(ev[1], ev[2]);
+    t.greedy_ms = hiphost::elapsed(ev[2], ev[3]);
+    t.total_ms = hiphost::elapsed(ev[0], ev[3]);
     t.n_components = n_components;
     t.n_large = n_large;
     t.cc_iterations = iterations;
     if (timing) *timing = t;
-    return 0;
+    return DSA_OK;
 }
