@@ -15,6 +15,8 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -134,7 +136,8 @@ struct dsa_ctx {
     DevBuf<uint8_t> d_ref, d_reads;
     DevBuf<dsa_fusion> d_fusions;
     int64_t upload_serial = 0;       // serial of the resident upload (unique over all contexts)
-    int nch_all = 1;                 // tiles of the widest window of the upload: refcodes stride = nch_all * W
+    int wt = W;                      // tile width in use of the upload (dsa_tile.hpp): picked for its widest window
+    int nch_all = 1;                 // tiles (of wt columns) of the widest window of the upload: refcodes stride = nch_all * W
     DevBuf<uint32_t> d_refcodes;     // packed once per run for the whole upload
     hipEvent_t ev_pack[2] = {};      // around k_pack_refs
     DevBuf<int32_t> d_orig;          // sweep order -> caller's pair index (Geom::orig)
@@ -198,6 +201,18 @@ int min_score_for(int lq)
     return (int)((double)f * 0.90);
 }
 
+// fn(std::integral_constant<int, WT>) for every built tile width (dsa_tile.hpp)
+template <class Fn, int... K>
+void for_each_tile_width_impl(Fn&& fn, std::integer_sequence<int, K...>)
+{
+    (fn(std::integral_constant<int, TILE_WIDTHS[K]>{}), ...);
+}
+template <class Fn>
+void for_each_tile_width(Fn&& fn)
+{
+    for_each_tile_width_impl(fn, std::make_integer_sequence<int, N_TILE_WIDTHS>{});
+}
+
 size_t slice_scratch_bytes(int64_t n_waves, int lq1, int nch)
 {
     size_t rows = (size_t)n_waves * lq1 * WAVE * 4;
@@ -232,6 +247,7 @@ void make_slices(dsa_ctx* ctx, int64_t n_pairs, int lqmax)
         cur.g.lq1 = lq1;
         cur.g.nch = ctx->nch_all;
         cur.g.lrp = ctx->nch_all * W;
+        cur.g.wt = ctx->wt;
         cur.g.n_fusions = ctx->n_fusions;
         cur.g.n_pairs = n;
         cur.g.orig = nullptr;                       // set when the buffers are known (enqueue_plan)
@@ -392,8 +408,8 @@ int launch_compute(dsa_ctx* ctx, PipeLane& L, const Slice& s)
 {
     Geom g = s.g;
 #ifdef DSA_PRUNE_STATS
-    HIPC(L.d_stats.reserve(16));
-    HIPC(hipMemsetAsync(L.d_stats.p, 0, 16 * sizeof(unsigned long long), L.stream));
+    HIPC(L.d_stats.reserve(DS_SLOTS));
+    HIPC(hipMemsetAsync(L.d_stats.p, 0, DS_SLOTS * sizeof(unsigned long long), L.stream));
     g.stats = L.d_stats.p;
 #endif
     hipStream_t st = L.stream;
@@ -411,19 +427,31 @@ int launch_compute(dsa_ctx* ctx, PipeLane& L, const Slice& s)
     const unsigned mask = L.tier_hint | 1u;
     L.tiers_launched = mask;
     g.tiers_launched = mask;
-    // (the instantiation with the in-register row-maximum reduction for 9-16 tiles only where a slice has that many:
-    // windows beyond 512 bases, e.g. 2x150 bp reads)
-#define DSA_LAUNCH_FILL(TIER, WIDE)                                                                                                              \
-    hipLaunchKernelGGL((k_fill_fast<TIER, WIDE>), dim3((unsigned)g.n_wgs), dim3(WG_LANES), 0, st, pairs, L.d_wg_tier.p, ctx->d_refcodes.p, \
-                       ctx->d_reads.p, L.d_rowcodes.p, L.d_rowbytes.p, ctx->d_min_score.p, ctx->d_fusions.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, L.d_tmask.p, fb, g)
+    // One instantiation per launch: the tile width in use of the upload, and the in-register row-maximum reduction for
+    // 9-16 tiles only where a slice has that many (windows beyond 512 bases, e.g. 2x150 bp reads).
     const bool wide = g.nch > 8 && g.nch <= 16;
-    if (wide) DSA_LAUNCH_FILL(0, true); else DSA_LAUNCH_FILL(0, false);
-    if (mask & 2u) { if (wide) DSA_LAUNCH_FILL(1, true); else DSA_LAUNCH_FILL(1, false); }
-    if (mask & 4u) { if (wide) DSA_LAUNCH_FILL(2, true); else DSA_LAUNCH_FILL(2, false); }
+    bool launched = false;
+    auto launch_fills = [&](auto wt_c, auto wide_c) {
+        constexpr int WT = decltype(wt_c)::value;
+        constexpr bool WIDE = decltype(wide_c)::value;
+        if (g.wt != WT || wide != WIDE) return;
+        launched = true;
+#define DSA_LAUNCH_FILL(TIER)                                                                                                                    \
+    hipLaunchKernelGGL((k_fill_fast<TIER, WIDE, WT>), dim3((unsigned)g.n_wgs), dim3(WG_LANES), 0, st, pairs, L.d_wg_tier.p, ctx->d_refcodes.p, \
+                       ctx->d_reads.p, L.d_rowcodes.p, L.d_rowbytes.p, ctx->d_min_score.p, ctx->d_fusions.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, L.d_tmask.p, fb, g)
+        DSA_LAUNCH_FILL(0);
+        if (mask & 2u) DSA_LAUNCH_FILL(1);
+        if (mask & 4u) DSA_LAUNCH_FILL(2);
 #undef DSA_LAUNCH_FILL
-    if (mask & 8u)
-        hipLaunchKernelGGL(k_fill_generic, dim3((unsigned)g.n_wgs), dim3(WG_LANES), 0, st, pairs, ctx->d_fusions.p, L.d_wg_tier.p, ctx->d_refcodes.p,
-                           ctx->d_reads.p, L.d_rowcodes.p, ctx->d_min_score.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, L.d_tmask.p, fb, g);
+        if (mask & 8u)
+            hipLaunchKernelGGL((k_fill_generic<WT>), dim3((unsigned)g.n_wgs), dim3(WG_LANES), 0, st, pairs, ctx->d_fusions.p, L.d_wg_tier.p, ctx->d_refcodes.p,
+                               ctx->d_reads.p, L.d_rowcodes.p, ctx->d_min_score.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, L.d_tmask.p, fb, g);
+    };
+    for_each_tile_width([&](auto wt_c) {
+        launch_fills(wt_c, std::false_type{});
+        launch_fills(wt_c, std::true_type{});
+    });
+    if (!launched) return fail(ctx, DSA_E_DEVICE, "internal: no fill kernel for tile width %d", g.wt);
     HIPC(hipEventRecord(L.ev[2], st));
     hipLaunchKernelGGL(k_replay, dim3(2048), dim3(REPLAY_BLOCK), 0, st, L.d_tasks.p, (uint64_t)L.d_tasks.cap, L.d_gtasks.p,
                        (uint64_t)L.d_gtasks.cap, L.d_ctr.p, L.d_state.p, L.d_kept.p, (uint64_t)L.d_kept.cap, pairs, ctx->d_fusions.p,
@@ -721,9 +749,13 @@ int dsa_get_limits(const dsa_ctx*, dsa_limits* out)
     // (dsa_long.hpp), about three orders of magnitude slower per cell
     out->max_read_len = LONG_MAX_READ;
     out->max_ref_len = LONG_MAX_REF;
-    out->tile_cols = W;
+    out->tile_cols = W;          // the widest tile; an upload may be swept in narrower ones (dsa_tile_cols_in_use)
     return DSA_OK;
 }
+
+int dsa_tile_cols_for(int32_t max_window) { return pick_tile_width(max_window); }
+
+int dsa_tile_cols_in_use(const dsa_ctx* ctx) { return ctx ? ctx->wt : 0; }
 
 const char* dsa_last_error(const dsa_ctx* ctx) { return ctx ? ctx->err.c_str() : "no context"; }
 
@@ -763,7 +795,7 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
     ctx->h_long_fusions.clear();
     ctx->long_cells = 0;
     ctx->long_blank_cells = 0;
-    int nch_all = 1, maxwin = 0;
+    int maxwin = 0;
     for (int32_t f = 0; f < n_fusions; ++f) {
         const dsa_fusion& fu = fusions[f];
         if (fu.ref0_len < 0 || fu.ref1_len < 0 || fu.ref0_off < 0 || fu.ref1_off < 0 ||
@@ -775,9 +807,15 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
             ctx->h_long_fusions.push_back(f);
             continue;
         }
-        nch_all = std::max<int>(nch_all, std::max(grid_of(fu.ref0_len, W), grid_of(fu.ref1_len, W)));
         maxwin = std::max(maxwin, std::max(fu.ref0_len, fu.ref1_len));
     }
+    // the tile width in use follows the widest window the tile kernels see (DEFUSE_DSA_TILE_COLS: one of the built widths, for A/B runs)
+    int wt = pick_tile_width(maxwin);
+    if (const char* e = getenv("DEFUSE_DSA_TILE_COLS")) {
+        if (!is_tile_width(atoi(e))) return fail(ctx, DSA_E_ARG, "DEFUSE_DSA_TILE_COLS=%s is not a built tile width", e);
+        wt = atoi(e);
+    }
+    const int nch_all = std::max(1, tiles_of(maxwin, wt));
     const bool any_long_fusion = !ctx->h_long_fusions.empty();
     int lqmax = 0;
     for (int64_t p = 0; p < n_pairs; ++p) {
@@ -821,6 +859,7 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
     HIPC(ctx->d_reads.reserve((size_t)read_bytes_len + 64));      // the planning kernels read whole dwords up to 36 bytes past a read's end
     HIPC(ctx->d_fusions.reserve((size_t)n_fusions + 1));
     HIPC(ctx->d_pairs_in.reserve((size_t)n_pairs + 1));
+    ctx->wt = wt;
     ctx->nch_all = nch_all;
     HIPC(ctx->d_refcodes.reserve((size_t)n_fusions * nch_all * W + 1));
     if (ref_bytes_len) HIPC(hipMemcpyAsync(ctx->d_ref.p, ref_bytes, ref_bytes_len, hipMemcpyHostToDevice, st));
@@ -851,7 +890,7 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
         ctx->plan_prm.n_fusions = n_fusions;
         ctx->plan_prm.slots = slots;
         ctx->plan_prm.wc = (mw + 2 * PLAN_PAD + 47) / 16 + 1;
-        ctx->plan_prm.tile_cols = W;
+        ctx->plan_prm.tile_cols = wt;
     }
     make_slices(ctx, n_pairs, lqmax);
     HIPC(hipGetLastError());

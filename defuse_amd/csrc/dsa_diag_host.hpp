@@ -26,7 +26,7 @@ inline void diag_dump_slice(const unsigned long long* d_stats, const uint2* d_gt
         for (int b = 0; b < 10; ++b) fprintf(stderr, " %ld", hist[k][b]);
         fprintf(stderr, "\n");
     }
-    unsigned long long h[16];
+    unsigned long long h[DS_SLOTS];
     (void)hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost);
     const double wc = h[DS_WAVE_CYCLES] ? (double)h[DS_WAVE_CYCLES] : 1.0;
     fprintf(stderr,
@@ -38,6 +38,14 @@ inline void diag_dump_slice(const unsigned long long* d_stats, const uint2* d_gt
     fprintf(stderr, "[stats] left-over replay: %llu waves, set-up %llu, sweep %llu cycles, %llu steps (lane 0); slowest lane of the listed count: %llu cycles, "
             "%llu kept rows, %llu tasks\n", h[DS_GREPLAY_WAVES], h[DS_GREPLAY_SETUP], h[DS_GREPLAY_SWEEP], h[DS_GREPLAY_STEPS], h[DS_SLOWEST_LISTED] >> 24,
             (h[DS_SLOWEST_LISTED] >> 8) & 0xFFFF, h[DS_SLOWEST_LISTED] & 0xFF);
+    // the table sweeps by tile index: where the swept row groups and the sweep cycles are (a narrower tile only pays in tiles that are swept)
+    unsigned long long tg = 0, tc = 0;
+    for (int c = 0; c < DS_TILE_SLOTS; ++c) { tg += h[DS_TILE_GROUPS + c]; tc += h[DS_TILE_CYCLES + c]; }
+    fprintf(stderr, "[stats] fill sweeps by tile, swept row groups %% / sweep cycles %%:");
+    for (int c = 0; c < DS_TILE_SLOTS; ++c)
+        if (h[DS_TILE_GROUPS + c] || h[DS_TILE_CYCLES + c])
+            fprintf(stderr, " t%d %.1f / %.1f", c, 100.0 * h[DS_TILE_GROUPS + c] / (tg ? tg : 1), 100.0 * h[DS_TILE_CYCLES + c] / (tc ? tc : 1));
+    fprintf(stderr, " (swept row groups %llu, sweep cycles %.4g)\n", tg, (double)tc);
 }
 
 inline void diag_dump_plan()

@@ -12,7 +12,8 @@
 //   * one lane = one candidate pair; its two matrices are packed as 2 x int16 per VGPR (lo = M1,
 //     hi = M2), so the recurrence needs no cross-lane traffic, every lane is busy whatever the
 //     number of reads per fusion, and pair p simply lives in wave p/64, lane p%64.
-//   * the matrices are swept in column tiles of W=64 reference positions held in 64 VGPRs; rows
+//   * the matrices are swept in column tiles of WT <= W = 64 reference positions held in WT VGPRs (the width in use WT
+//     is chosen per upload, dsa_tile.hpp, and is a template parameter of the kernels that sweep); rows
 //     (read bases) are the outer runtime loop.  State V(i,j) = H(i,j) + 2j makes the "left" move free:
 //         V(i,j) = max( V(i-1,j-1) + (eq ? 4 : 1),  V(i-1,j) - 2,  V(i,j-1) )
 //     one ascending pass per row, in place:  X[i] = max3(Xold[i-1] + d(i), Xold[i], Xnew[i-1] - 2)
@@ -45,10 +46,12 @@
 
 #include "../../include/defuse_dsa.h"
 #include "dsa_diag.hpp"
+#include "dsa_tile.hpp"
 
 namespace dsa {
 
-constexpr int W = 64;                 // tile width (reference columns per register tile)
+constexpr int W = TILE_W;             // widest tile and storage width of a tile (reference codes, table rows, column masks); a run sweeps
+                                      // the first Geom::wt <= W columns of every tile, the others do not exist (dsa_tile.hpp)
 constexpr int WAVE = 64;
 constexpr int WG_WAVES = 4;           // waves per workgroup of the fill kernels
 constexpr int WG_LANES = WG_WAVES * WAVE;
@@ -189,7 +192,8 @@ struct Geom {
     int32_t n_wgs;
     int32_t lq1;           // rows stride  = max read length + 1
     int32_t nch;           // chunk stride = max n_chunks
-    int32_t lrp;           // refcodes stride = nch * W
+    int32_t lrp;           // refcodes stride = nch * W: tile c of a window starts at c * W, its columns wt..W-1 are padding
+    int32_t wt;            // tile width in use: column i of tile c is reference position c * wt + i
     int32_t n_fusions;
     int64_t n_pairs;
     const int32_t* orig;   // pair order of the sweep -> the caller's pair index (nullptr: the same order)
@@ -266,7 +270,7 @@ __device__ __forceinline__ int half_of(uint32_t v, int h) { return (int)((v >> (
 
 // ---------------------------------------------------------------------------------------------
 // K0: byte -> packed code, code16 = byte<<8.
-//   refcodes[f*lrp + i]        = { lo: ref0[i],            hi: ref1[len1-1-i] }   (pad beyond the end)
+//   refcodes[f*lrp + c*W + k]  = { lo: ref0[i],            hi: ref1[len1-1-i] },  i = c*wt + k, k < wt   (pad beyond the end and for k >= wt)
 //   rowcodes[(w*lq1 + j)*64+l] = { lo: read[j-1],          hi: read[lq-j]     }   of pair w*64+l
 // ---------------------------------------------------------------------------------------------
 __global__ void k_pack_refs(const uint8_t* __restrict__ ref_bytes, const dsa_fusion* __restrict__ fusions,
@@ -275,9 +279,14 @@ __global__ void k_pack_refs(const uint8_t* __restrict__ ref_bytes, const dsa_fus
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t total = (int64_t)g.n_fusions * g.lrp;
     if (t >= total) return;
-    const int i = (int)(t % g.lrp);
+    const int s = (int)(t % g.lrp), k = s % W;
+    const int i = (s / W) * g.wt + k;
     const dsa_fusion f = fusions[t / g.lrp];
     uint32_t lo = REF_PAD16, hi = REF_PAD16;
+    if (k >= g.wt) {
+        refcodes[t] = lo | (hi << 16);
+        return;
+    }
     if (i < f.ref0_len) lo = (uint32_t)ref_bytes[(int64_t)f.ref0_off + i] << 8;
     if (i < f.ref1_len) hi = (uint32_t)ref_bytes[(int64_t)f.ref1_off + (f.ref1_len - 1 - i)] << 8;
     refcodes[t] = lo | (hi << 16);
@@ -309,12 +318,12 @@ __device__ __forceinline__ void table_row_classes(int t, int& k1, int& k2)   // 
 // Score tables of one tile for the fusion groups of a workgroup (layout: k_fill_fast).  One thread per
 // (group, column): the five per-class terms of either field are formed once and combined into the 25
 // table rows, so a tile's tables cost ~100 instructions per thread.  code_of(gi, i, q0, q1) returns the
-// 16-bit reference codes of column i (REF_PAD16 = padding) for M1 / M2.
-template <bool SPLIT, class CodeFn>
+// 16-bit reference codes of column i < WT (REF_PAD16 = padding) for M1 / M2.
+template <bool SPLIT, int WT, class CodeFn>
 __device__ __forceinline__ void build_tables(uint32_t* __restrict__ T, int n_groups, CodeFn&& code_of)
 {
-    for (int e = threadIdx.x; e < n_groups * W; e += WG_LANES) {
-        const int i = e & (W - 1), gi = e >> 6;
+    for (int e = threadIdx.x; e < n_groups * WT; e += WG_LANES) {
+        const int i = e % WT, gi = e / WT;
         uint32_t q0, q1;
         code_of(gi, i, q0, q1);
         const uint32_t cls_byte[NCLS] = {'A', 'C', 'T', 'G', 'N'};   // inverse of base_class
@@ -390,7 +399,8 @@ __device__ __forceinline__ bool pack_rows_wave(const uint8_t* __restrict__ read_
 //   bprev = V(i0-1, j-1), bcur = V(i0-1, j)   (the previous tile's last column; V=0 for tile 0)
 // The next column's diagonal term is formed before X[i] is overwritten, so the update is in place.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void row_step(uint32_t (&X)[W], const uint32_t (&r)[W], uint32_t cj, uint32_t bprev,
+template <int WT>
+__device__ __forceinline__ void row_step(uint32_t (&X)[WT], const uint32_t (&r)[WT], uint32_t cj, uint32_t bprev,
                                          uint32_t bcur)
 {
     // X[i] carries drift 2i; bprev/bcur are drift-free.  Diagonal into column i>0 gains +2 of drift.
@@ -402,13 +412,13 @@ __device__ __forceinline__ void row_step(uint32_t (&X)[W], const uint32_t (&r)[W
     uint32_t a = (bprev + FOUR2) - min3u(cj ^ r[0]);
     uint32_t up = bcur - TWO2;
 #pragma unroll
-    for (int b = 0; b < W; b += BLK) {
+    for (int b = 0; b < WT; b += BLK) {
         uint32_t d[BLK];
 #pragma unroll
         for (int k = 0; k < BLK; ++k)
-            d[k] = b + k + 1 < W ? SIX2 - min3u(cj ^ r[b + k + 1]) : 0u;
+            d[k] = b + k + 1 < WT ? SIX2 - min3u(cj ^ r[b + k + 1]) : 0u;
 #pragma unroll
-        for (int k = 0; k < BLK; ++k) {
+        for (int k = 0; k < BLK && b + k < WT; ++k) {
             const int i = b + k;
             const uint32_t a_next = X[i] + d[k];
             X[i] = max3(a, X[i], up);
@@ -420,12 +430,13 @@ __device__ __forceinline__ void row_step(uint32_t (&X)[W], const uint32_t (&r)[W
 
 // tile row maximum: one max3 per two columns, two interleaved accumulators.
 // MASKED: only columns < nv0 (lo field) / nv1 (hi field) count.
-template <bool MASKED>
-__device__ __forceinline__ uint32_t tile_row_max(const uint32_t (&X)[W], int nv0, int nv1)
+template <bool MASKED, int WT>
+__device__ __forceinline__ uint32_t tile_row_max(const uint32_t (&X)[WT], int nv0, int nv1)
 {
     uint32_t acc0 = BIAS2, acc1 = BIAS2;      // V >= 0 everywhere, so V = 0 is neutral
+    static_assert(WT % 4 == 0, "four columns per step");
 #pragma unroll
-    for (int i = 0; i < W; i += 4) {
+    for (int i = 0; i < WT; i += 4) {
         uint32_t x[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -537,7 +548,7 @@ __device__ __forceinline__ void wave_alloc4(Counters* ctr, const unsigned (&n)[4
 // re-reads only what it stored itself.  All threads of the workgroup must call it (barriers inside).
 // fl->tile[k] returns the tile pair agreed for the table-driven replay of fusion group k (-1: none);
 // HANDOFF also fills fl->info / fl->kc for replay_fast_wg.
-template <bool HANDOFF>
+template <bool HANDOFF, int WT>
 __device__ __forceinline__ void combine_wg(
     const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions, const uint32_t* __restrict__ cmax,
     const uint32_t* __restrict__ rmax, const uint32_t* __restrict__ tmask, const int32_t* __restrict__ min_score_tab,
@@ -579,8 +590,8 @@ __device__ __forceinline__ void combine_wg(
         lq = pr.read_len;
         len0 = fu.ref0_len;
         len1 = fu.ref1_len;
-        nc0 = cdiv_dev(fu.ref0_len, W);
-        nc1 = cdiv_dev(fu.ref1_len, W);
+        nc0 = cdiv_dev(fu.ref0_len, WT);
+        nc1 = cdiv_dev(fu.ref1_len, WT);
         small = nc0 <= 64 && nc1 <= 64;
         const int min_score = min_score_tab[lq];
         if (g.nch <= TMASK_TILES) {
@@ -772,9 +783,9 @@ __device__ __forceinline__ void combine_wg(
         li.c1 = here ? (uint8_t)c1 : NO_CHUNK;
         li.key_group = (uint16_t)((fold_a < 255 ? fold_a : 255) | ((gsel >= 0 ? gsel : 0) << 8));
         li.lq = (uint16_t)lq;
-        const int v0 = len0 - c0 * W, v1 = len1 - c1 * W;
-        li.nv0 = (uint8_t)(here && c0 != NO_CHUNK ? (v0 < W ? (v0 > 0 ? v0 : 0) : W) : 0);
-        li.nv1 = (uint8_t)(here && c1 != NO_CHUNK ? (v1 < W ? (v1 > 0 ? v1 : 0) : W) : 0);
+        const int v0 = len0 - c0 * WT, v1 = len1 - c1 * WT;
+        li.nv0 = (uint8_t)(here && c0 != NO_CHUNK ? (v0 < WT ? (v0 > 0 ? v0 : 0) : WT) : 0);
+        li.nv1 = (uint8_t)(here && c1 != NO_CHUNK ? (v1 < WT ? (v1 > 0 ? v1 : 0) : WT) : 0);
         fl->info[tid] = li;
     }
     if (!active) return;
@@ -893,9 +904,10 @@ __device__ __forceinline__ HitCursor cursor_init(const KeptRow* __restrict__ kr,
 // sat(X - (target - 1 + drift)) is 1 exactly on a hit: one add (drift), one saturating packed subtract
 // and one shift-or into a hit-bit accumulator.
 constexpr uint32_t NO_TARGET16 = 0x7F00u;   // above BIAS16 + 4 * 7600 + drift, and + drift still fits the field
-__device__ __forceinline__ void equal_columns(const uint32_t (&X)[W], uint32_t target2, uint64_t& m0, uint64_t& m1)
+template <int WT>
+__device__ __forceinline__ void equal_columns(const uint32_t (&X)[WT], uint32_t target2, uint64_t& m0, uint64_t& m1)
 {
-    uint32_t hit[W / 16];
+    uint32_t hit[W / 16];                       // bits of the columns WT..W-1 stay 0
     const uint32_t below = target2 - 0x00010001u;
 #pragma unroll
     for (int q = 0; q < W / 16; ++q) {
@@ -903,6 +915,7 @@ __device__ __forceinline__ void equal_columns(const uint32_t (&X)[W], uint32_t t
 #pragma unroll
         for (int k = 15; k >= 0; --k) {
             const int i = 16 * q + k;
+            if (i >= WT) continue;
             const uint32_t c = below + drift2(i);
             typedef unsigned short us2 __attribute__((ext_vector_type(2)));
             const uint32_t y = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(us2, X[i]), __builtin_bit_cast(us2, c)));   // v_pk_sub_u16 clamp
@@ -918,7 +931,8 @@ __device__ __forceinline__ void equal_columns(const uint32_t (&X)[W], uint32_t t
 }
 
 // At row j: report, for the kept rows met here, the valid columns that attain the row maximum.
-__device__ __forceinline__ void record_hits(const uint32_t (&X)[W], int j, int lq, const KeptRow* __restrict__ kr,
+template <int WT>
+__device__ __forceinline__ void record_hits(const uint32_t (&X)[WT], int j, int lq, const KeptRow* __restrict__ kr,
                                             const uint64_t* kc, int n_kept, bool has0, bool has1, HitCursor& hc,
                                             uint64_t* __restrict__ masks, uint32_t mask_begin)
 {
@@ -966,7 +980,7 @@ __device__ __forceinline__ int64_t count_one_tile_pair(const uint64_t* mk, int n
 // LDS score tables as the fill (no row maxima, no stores: add + max3 per column).  Called by all
 // threads of the workgroup after combine_wg<true>, whose LDS hand-off (fl) says what to replay; T is
 // free by then (barriers inside combine_wg).
-template <bool SPLIT>
+template <bool SPLIT, int WT>
 __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const WgView& wgi, const FinishBufs& fb,
                                                const uint32_t* __restrict__ refcodes, const uint32_t* __restrict__ rowcodes,
                                                const uint32_t* __restrict__ bnd, const Geom& g)
@@ -977,7 +991,7 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
     for (int k = 0; k < wgi.n_groups; ++k) any |= fl->tile[k] >= 0;
     if (!any) return;                                   // uniform
     // tables for the agreed tile pair of every fusion of the workgroup
-    build_tables<SPLIT>(T, wgi.n_groups, [&](int gi, int i, uint32_t& q0, uint32_t& q1) {
+    build_tables<SPLIT, WT>(T, wgi.n_groups, [&](int gi, int i, uint32_t& q0, uint32_t& q1) {
         const int key = fl->tile[gi];
         q0 = q1 = REF_PAD16;                 // no tile agreed: nobody reads this group's table
         if (key >= 0) {
@@ -1037,9 +1051,9 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
     const int stop0 = c0 > 0 ? load_tstop(fb.tstop + wr * g.nch + (c0 - 1)) : 0;   // stored row groups of the tiles to the left
     const int stop1 = c1 > 0 ? load_tstop(fb.tstop + wr * g.nch + (c1 - 1)) : 0;
 
-    uint32_t X[W];
+    uint32_t X[WT];
 #pragma unroll
-    for (int i = 0; i < W; ++i) X[i] = BIAS2 + drift2(i);
+    for (int i = 0; i < WT; ++i) X[i] = BIAS2 + drift2(i);
     const uint4 bias4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint32_t bprev = BIAS2;
     const int ngq = (Rw >> 2) + 1;
@@ -1071,9 +1085,9 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
                 uint32_t a = bprev + v.x;
                 uint32_t up = bcur - TWO2;
 #pragma unroll
-                for (int q = 0; q < W / 4; ++q) {
+                for (int q = 0; q < WT / 4; ++q) {
                     uint4 vn = v;
-                    if (q + 1 < W / 4) vn = table4(q + 1);
+                    if (q + 1 < WT / 4) vn = table4(q + 1);
                     uint32_t an;
                     an = X[4 * q + 0] + v.y;
                     X[4 * q + 0] = max3(a, X[4 * q + 0], up);
@@ -1114,15 +1128,15 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
 // 2*Lq - minScore, l_in the last row at which a live value can still enter from the left, stop_prev the
 // stored row groups of the tile to the left.  Returns the row groups stored for this tile; last_bnd is
 // the last row whose outgoing boundary is alive for this lane.
-template <bool MASKED>
-__device__ __forceinline__ int sweep_tile_generic(const uint32_t (&r)[W], const uint4* __restrict__ rows4,
+template <bool MASKED, int WT>
+__device__ __forceinline__ int sweep_tile_generic(const uint32_t (&r)[WT], const uint4* __restrict__ rows4,
                                                   const uint4* __restrict__ bi4, uint4* __restrict__ cm4,
                                                   uint4* __restrict__ bo4, int lq, bool first, int nv0, int nv1,
                                                   int lq_lane, int slack, int l_in, int stop_prev, int& last_bnd)
 {
-    uint32_t X[W];
+    uint32_t X[WT];
 #pragma unroll
-    for (int i = 0; i < W; ++i) X[i] = BIAS2 + drift2(i);
+    for (int i = 0; i < WT; ++i) X[i] = BIAS2 + drift2(i);
     const uint4 bias4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint32_t bprev = BIAS2;
     const int ngq = (lq >> 2) + 1;
@@ -1144,7 +1158,7 @@ __device__ __forceinline__ int sweep_tile_generic(const uint32_t (&r)[W], const 
             if (j >= 1 && j <= lq) {                        // wave-uniform
                 row_step(X, r, rcv[sidx], bprev, bv[sidx]);
                 cmv[sidx] = tile_row_max<MASKED>(X, nv0, nv1);
-                bov[sidx] = X[W - 1] - drift2(W - 1);
+                bov[sidx] = X[WT - 1] - drift2(WT - 1);
                 const int thr = 4 * j - slack + (int)BIAS16;
                 const bool in_read = j <= lq_lane;
                 alive |= in_read && ((int)(cmv[sidx] & 0xFFFFu) >= thr || (int)(cmv[sidx] >> 16) >= thr);
@@ -1275,6 +1289,7 @@ __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax
     }
 }
 
+template <int WT>
 __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __restrict__ pairs,
                                                            const dsa_fusion* __restrict__ fusions,
                                                            const uint8_t* __restrict__ wg_tier,
@@ -1303,7 +1318,7 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
         };
         WaveInfo wi;                             // rows and tiles of the wave, from its own pairs
         wi.lq_max = wave_max(in_batch ? (int)pairs[p].read_len : 0);
-        wi.nch_max = wave_max(in_batch ? max(cdiv_dev(fu.ref0_len, W), cdiv_dev(fu.ref1_len, W)) : 0);
+        wi.nch_max = wave_max(in_batch ? max(cdiv_dev(fu.ref0_len, WT), cdiv_dev(fu.ref1_len, WT)) : 0);
         (void)pack_rows_wave<0>(read_bytes, pairs, rowcodes, nullptr, g, w, lane, wi.lq_max);   // the fast kernel packs only what it keeps
         const uint32_t* rc = refcodes + (int64_t)f * g.lrp;
         const uint4* rows4 = reinterpret_cast<const uint4*>(rowcodes + (int64_t)w * g.lq1 * WAVE) + lane;
@@ -1317,18 +1332,18 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
         TileStops stops = {};
 
         for (int c = 0; c < wi.nch_max; ++c) {
-            uint32_t r[W];
+            uint32_t r[WT];
 #pragma unroll
-            for (int i = 0; i < W; ++i) r[i] = rc[c * W + i];
-            const int nv0 = fu.ref0_len - c * W, nv1 = fu.ref1_len - c * W;   // per lane; may be <= 0
+            for (int i = 0; i < WT; ++i) r[i] = rc[c * W + i];
+            const int nv0 = fu.ref0_len - c * WT, nv1 = fu.ref1_len - c * WT;   // per lane; may be <= 0
             uint4* cm4 = reinterpret_cast<uint4*>(cmax + ((int64_t)w * g.nch + c) * g.lq1 * WAVE) + lane;
             uint4* bo4 = reinterpret_cast<uint4*>(bnd + ((int64_t)w * g.nch + c) * g.lq1 * WAVE) + lane;
             const uint4* bi4 = reinterpret_cast<const uint4*>(bnd + ((int64_t)w * g.nch + (c - 1)) * g.lq1 * WAVE) + lane;
             int last_bnd, stop;
-            if (__builtin_amdgcn_ballot_w64(nv0 < W || nv1 < W) == 0)
-                stop = sweep_tile_generic<false>(r, rows4, bi4, cm4, bo4, wi.lq_max, c == 0, nv0, nv1, lq_lane, slack, l_in, stop_prev, last_bnd);
+            if (__builtin_amdgcn_ballot_w64(nv0 < WT || nv1 < WT) == 0)
+                stop = sweep_tile_generic<false, WT>(r, rows4, bi4, cm4, bo4, wi.lq_max, c == 0, nv0, nv1, lq_lane, slack, l_in, stop_prev, last_bnd);
             else
-                stop = sweep_tile_generic<true>(r, rows4, bi4, cm4, bo4, wi.lq_max, c == 0, nv0, nv1, lq_lane, slack, l_in, stop_prev, last_bnd);
+                stop = sweep_tile_generic<true, WT>(r, rows4, bi4, cm4, bo4, wi.lq_max, c == 0, nv0, nv1, lq_lane, slack, l_in, stop_prev, last_bnd);
             if (lane == 0) fb.tstop[(int64_t)w * g.nch + c] = stop;
             stop_prev = stop;
 #pragma unroll
@@ -1341,24 +1356,25 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
     }
     WgView wgi = {};                             // no tables, no groups: every task goes to k_replay
     wgi.list = nullptr;
-    combine_wg<false>(pairs, fusions, cmax, rmax, tmask, min_score_tab, wgi, 0, false, &fl, fb, g);
+    combine_wg<false, WT>(pairs, fusions, cmax, rmax, tmask, min_score_tab, wgi, 0, false, &fl, fb, g);
 }
 
 // The sweep of one tile by one wave of the table kernels (TIER 0: 25-row tables, SPLIT: two 5-row tables per fusion): rows in
 // groups of four, per row one ascending pass over the tile's NW columns — four columns per table read, the diagonal term of the
 // next column formed from X[i] before X[i] is overwritten, the chain max3 -> max3 — the tile's row maximum and, unless the tile
-// is the wave's last (LAST: nothing reads it), its boundary column.  NW = 64; a 16-column instantiation for a last tile of which
-// no lane has more than 16 columns (windows of 389 = 6 x 64 + 5 bases) exists behind -DDSA_NARROW only: measured on one box
-// against the same build without it, the fill took 3.100 instead of 3.050 ms — the second copy of the loop costs more
-// (instruction cache, register allocation) than the quarter-width seventh pass saves.  Exact pruning as described at the
-// kernel.  Returns the row groups stored for the tile; last_bnd = last row whose outgoing boundary is alive (this lane).
+// is the wave's last (LAST: nothing reads it), its boundary column.  NW is the launch's tile width in use and the same for every
+// tile: a kernel holds ONE width of the unrolled loop.  (A second, 16-column copy for a last tile of 5 columns — windows of
+// 389 = 6 x 64 + 5 bases — measured slower than none, 3.100 against 3.050 ms: it costs more instruction cache and registers
+// than the narrow pass saves.  The width is therefore picked per upload and each launch runs the instantiation for it.)
+// Exact pruning as described at the kernel.  `tile` is the tile's index (statistics of the diagnostic builds only).
+// Returns the row groups stored for the tile; last_bnd = last row whose outgoing boundary is alive (this lane).
 template <int NW, bool SPLIT, bool LAST>
 __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, const uint32_t* __restrict__ rows1, const uint4* __restrict__ bi4,
                                                uint4* __restrict__ cm4, uint4* __restrict__ bo4, bool first_tile, int lq_max, int lq_lane,
-                                               int slack, int l_in, int stop_prev, int& last_bnd, const Geom& g)
+                                               int slack, int l_in, int stop_prev, int& last_bnd, const Geom& g, int tile)
 {
-    static_assert(NW % 4 == 0 && NW / 4 > FILL_PF, "table reads in flight");
-    (void)g;
+    static_assert(NW % 4 == 0 && NW / 4 > FILL_PF && NW <= W, "table reads in flight");
+    (void)g; (void)tile;
     uint32_t X[NW];
 #pragma unroll
     for (int i = 0; i < NW; ++i) X[i] = BIAS2 + drift2(i);
@@ -1507,6 +1523,7 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
         DSA_STAT_ADD(g, DS_GAP_GROUPS, n_gap_groups);
         DSA_STAT_ADD(g, DS_GROUPS_SKIPPED, ngq - gq);
         DSA_STAT_ADD(g, DS_GROUPS, ngq);
+        DSA_STAT_ADD(g, DS_TILE_GROUPS + (tile < DS_TILE_SLOTS ? tile : DS_TILE_SLOTS - 1), gq - n_gap_groups);
     }
     return gq;
 }
@@ -1527,7 +1544,7 @@ __host__ __device__ constexpr int tier_of(int n_groups) { return n_groups <= GMA
 #ifndef DSA_FAST_WGS
 #define DSA_FAST_WGS 4        // workgroups (of four waves) per CU the table tiers 0 and 1 are compiled for
 #endif
-template <int TIER, bool WIDE = false>
+template <int TIER, bool WIDE, int WT>
 __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill_fast(const dsa_pair* __restrict__ pairs,
                                                            uint8_t* __restrict__ wg_tier,
                                                            const uint32_t* __restrict__ refcodes,
@@ -1570,13 +1587,12 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
     // 4), and no live cell's value comes from a dead cell.  Once a whole tile row and everything that
     // can still enter from the left are dead, the rest of the tile is dead: the sweep stops there and
     // stores "V = 0" for the remaining rows (a lower bound, which is all dead cells need to be).
-    int lq_lane = 0, slack = 0, tiles_lane = 0, tail_cols_lane = 0;
+    int lq_lane = 0, slack = 0, tiles_lane = 0;
     if (in_batch) {
         const dsa_fusion fu = fusions[f];
         lq_lane = pr.read_len;
         slack = 2 * lq_lane - max(min_score_tab[lq_lane], pair_bound(pr));
-        tiles_lane = max(cdiv_dev(fu.ref0_len, W), cdiv_dev(fu.ref1_len, W));
-        tail_cols_lane = max(fu.ref0_len, fu.ref1_len) - (tiles_lane - 1) * W;       // columns of the longer window in its last tile
+        tiles_lane = max(cdiv_dev(fu.ref0_len, WT), cdiv_dev(fu.ref1_len, WT));
     }
     auto wave_max = [](int v) {
 #pragma unroll
@@ -1611,15 +1627,13 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
     int stop_prev = 0;                   // stored row groups of the tile to the left
     TileStops stops = {};
 
-    // columns the lane has in the wave's last tile (wave-uniform maximum): 16 or fewer in every lane -> the narrow sweep
-    const int tail_cols = wave_max(in_batch && tiles_lane == wi.nch_max ? tail_cols_lane : 0);
     DiagClock clk_all, clk;
     unsigned long long t_bar = 0, t_tab = 0;
     for (int c = 0; c < nch_wg; ++c) {
         clk.lap();
         __syncthreads();                          // previous tile's tables no longer in use
         t_bar += clk.lap();
-        build_tables<SPLIT>(T, wgi.n_groups, [&](int gi, int i, uint32_t& q0, uint32_t& q1) {
+        build_tables<SPLIT, WT>(T, wgi.n_groups, [&](int gi, int i, uint32_t& q0, uint32_t& q1) {
             const uint32_t code = refcodes[(int64_t)group_fusion(wgi, gi) * g.lrp + c * W + i];
             q0 = code & 0xFFFFu;
             q1 = code >> 16;
@@ -1634,11 +1648,10 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
         const uint4* bi4 = reinterpret_cast<const uint4*>(bnd + ((int64_t)w * g.nch + (c - 1)) * g.lq1 * WAVE) + lane;
         int last_bnd = 0, gq;
         if (c + 1 < wi.nch_max)
-            gq = sweep_tile_fast<W, SPLIT, false>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g);
-        else if (!DIAG_NARROW || tail_cols > 16)
-            gq = sweep_tile_fast<W, SPLIT, true>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g);
-        else       // (-DDSA_NARROW builds only, see dsa_diag.hpp)
-            gq = sweep_tile_fast<16, SPLIT, true>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g);
+            gq = sweep_tile_fast<WT, SPLIT, false>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g, c);
+        else
+            gq = sweep_tile_fast<WT, SPLIT, true>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g, c);
+        if (lane == 0) DSA_STAT_ADD(g, DS_TILE_CYCLES + (c < DS_TILE_SLOTS ? c : DS_TILE_SLOTS - 1), clk.lap());
         // the dead remainder of the tile is not stored: its readers substitute V = 0 past the stop
         if (lane == 0) fb.tstop[(int64_t)w * g.nch + c] = gq;
         stop_prev = gq;
@@ -1657,9 +1670,9 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
         t_rowmax = clk.lap();
         // The latency-bound finish work of this workgroup runs here, in the shadow of the other resident
         // workgroups' sweeps, instead of in kernels of its own.
-        combine_wg<true>(pairs, fusions, cmax, rmax, tmask, min_score_tab, wgi, my_group, true, &fl, fb, g);
+        combine_wg<true, WT>(pairs, fusions, cmax, rmax, tmask, min_score_tab, wgi, my_group, true, &fl, fb, g);
         t_combine = clk.lap();
-        if (DIAG_REPLAY) replay_fast_wg<SPLIT>(T, &fl, wgi, fb, refcodes, rowcodes, bnd, g);
+        if (DIAG_REPLAY) replay_fast_wg<SPLIT, WT>(T, &fl, wgi, fb, refcodes, rowcodes, bnd, g);
         t_replay = clk.lap();
     }
     if (lane == 0 && live) {
@@ -1804,8 +1817,8 @@ __global__ __launch_bounds__(REPLAY_BLOCK, 5) void k_replay(const ReplayTask* __
 #pragma unroll
         for (int i = 0; i < RW; ++i) X[i] = BIAS2 + drift2(i);
         const int R = rt.last_row & TASK_ROW;
-        const int nv0 = has0 ? min(W, fu.ref0_len - c0 * W) : 0;
-        const int nv1 = has1 ? min(W, fu.ref1_len - c1 * W) : 0;
+        const int nv0 = has0 ? min(g.wt, fu.ref0_len - c0 * g.wt) : 0;    // (the quarters sweep all W stored columns: those past wt are padding)
+        const int nv1 = has1 ? min(g.wt, fu.ref1_len - c1 * g.wt) : 0;
         // kept rows ascend in a: M1 (row a) meets them in order k=0.., M2 (row lq-a) in reverse
         {
             const uint2* kr2 = reinterpret_cast<const uint2*>(kr);
@@ -1911,9 +1924,9 @@ __global__ void k_publish(const Counters* __restrict__ ctr, const int64_t* __res
 // order (tools/SplitReadAligner.cpp:233-269), then the refSplit de-duplication of
 // tools/SplitAlignment.cpp:381-391 (first occurrence wins).  WRITE=false counts.
 __device__ __forceinline__ bool col_in(const ReplayTask* tasks, const uint64_t* masks, uint32_t tb, uint32_t te,
-                                       int k, int h, int col /*1-based matrix column*/)
+                                       int k, int h, int col /*1-based matrix column*/, int wt)
 {
-    const int c = (col - 1) / W, bit = (col - 1) % W;
+    const int c = (col - 1) / wt, bit = (col - 1) % wt;
     for (uint32_t q = tb; q < te; ++q)
         if ((h ? tasks[q].chunk1 : tasks[q].chunk0) == c)
             return (masks[((uint64_t)tasks[q].mask_begin + k) * 2 + h] >> bit) & 1ull;
@@ -1931,13 +1944,13 @@ struct EmitLds {
     uint2 kept[SLOTS][EMIT_BLOCK];   // the kept rows
 };
 
-// The records of one pair (WRITE) or their number.
+// The records of one pair (WRITE) or their number.  wt = Geom::wt: bit b of a mask of tile c is matrix column c * wt + b + 1.
 template <bool WRITE, int SLOTS>
 __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int64_t o, const PairState& st, const dsa_pair* __restrict__ pairs,
                                              const dsa_fusion* __restrict__ fusions, const KeptRow* __restrict__ kept,
                                              const ReplayTask* __restrict__ tasks, const uint64_t* __restrict__ masks,
                                              const int64_t* __restrict__ rec_offset, dsa_record* __restrict__ out, uint64_t out_cap,
-                                             int64_t pair_base)
+                                             int64_t pair_base, int wt)
 {
     const int tid = threadIdx.x;
     int64_t n = 0;
@@ -2001,7 +2014,7 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
             }
         }
         const bool both = st.tiles0 != 0 && st.tiles1 != 0;
-        const int base1 = __builtin_ctz(st.tiles0 | 0x10000u) * W + 1, base2 = __builtin_ctz(st.tiles1 | 0x10000u) * W + 1;
+        const int base1 = __builtin_ctz(st.tiles0 | 0x10000u) * wt + 1, base2 = __builtin_ctz(st.tiles1 | 0x10000u) * wt + 1;
         auto lo64 = [](const uint4& v) -> uint64_t { return ((uint64_t)v.y << 32) | v.x; };
         auto hi64 = [](const uint4& v) -> uint64_t { return ((uint64_t)v.w << 32) | v.z; };
 #pragma unroll
@@ -2058,7 +2071,7 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
                             const int b2 = __builtin_ctzll(r2);
                             bool dup = false;
                             for (int k2 = 0; k2 < k && !dup; ++k2) dup = ((mask_of(k2, t1, 0) >> b1) & 1ull) && ((mask_of(k2, t2, 1) >> b2) & 1ull);
-                            if (!dup) put(c0 * W + b1 + 1, c1 * W + b2 + 1, kr);
+                            if (!dup) put(c0 * wt + b1 + 1, c1 * wt + b2 + 1, kr);
                         }
                     }
                 }
@@ -2073,17 +2086,17 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
                 if (tasks[q1].chunk0 == NO_CHUNK) continue;
                 uint64_t m1 = masks[((uint64_t)tasks[q1].mask_begin + k) * 2];
                 while (m1) {
-                    const int i1 = tasks[q1].chunk0 * W + __builtin_ctzll(m1) + 1;
+                    const int i1 = tasks[q1].chunk0 * wt + __builtin_ctzll(m1) + 1;
                     m1 &= m1 - 1;
                     for (uint32_t q2 = tb; q2 < te; ++q2) {
                         if (tasks[q2].chunk1 == NO_CHUNK) continue;
                         uint64_t m2 = masks[((uint64_t)tasks[q2].mask_begin + k) * 2 + 1];
                         while (m2) {
-                            const int i2 = tasks[q2].chunk1 * W + __builtin_ctzll(m2) + 1;
+                            const int i2 = tasks[q2].chunk1 * wt + __builtin_ctzll(m2) + 1;
                             m2 &= m2 - 1;
                             bool dup = false;     // same refSplit <=> same (i1,i2) at an earlier kept a
                             for (int k2 = 0; k2 < k && !dup; ++k2)
-                                dup = col_in(tasks, masks, tb, te, k2, 0, i1) && col_in(tasks, masks, tb, te, k2, 1, i2);
+                                dup = col_in(tasks, masks, tb, te, k2, 0, i1, wt) && col_in(tasks, masks, tb, te, k2, 1, i2, wt);
                             if (!dup) put(i1, i2, kr);
                         }
                     }
@@ -2103,7 +2116,7 @@ __device__ __forceinline__ int64_t emit_pair_wave(EmitLds<SLOTS>* lds, int64_t p
                                                   uint32_t tiles0, uint32_t tiles1, int first0, int first1, const dsa_pair* __restrict__ pairs,
                                                   const dsa_fusion* __restrict__ fusions, const KeptRow* __restrict__ kept,
                                                   const uint64_t* __restrict__ masks, const int64_t* __restrict__ rec_offset,
-                                                  dsa_record* __restrict__ out, uint64_t out_cap, int64_t pair_base)
+                                                  dsa_record* __restrict__ out, uint64_t out_cap, int64_t pair_base, int wt)
 {
     const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
     auto slot_m = [&](int e) -> uint4& { return lds->mask[e >> 6][wbase + (e & 63)]; };
@@ -2148,7 +2161,7 @@ __device__ __forceinline__ int64_t emit_pair_wave(EmitLds<SLOTS>* lds, int64_t p
                         const int b2 = __builtin_ctzll(r2);
                         bool dup = false;
                         for (int k2 = 0; k2 < k && !dup; ++k2) dup = ((mask_of(k2, t1, 0) >> b1) & 1ull) && ((mask_of(k2, t2, 1) >> b2) & 1ull);
-                        if (!dup) fn(c0 * W + b1 + 1, c1 * W + b2 + 1);
+                        if (!dup) fn(c0 * wt + b1 + 1, c1 * wt + b2 + 1);
                     }
                 }
             }
@@ -2203,7 +2216,7 @@ __device__ __forceinline__ int64_t emit_heavy_of_wave(EmitLds<SLOTS>* lds, bool 
                                                       const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions,
                                                       const KeptRow* __restrict__ kept, const uint64_t* __restrict__ masks,
                                                       const int64_t* __restrict__ rec_offset, dsa_record* __restrict__ out, uint64_t out_cap,
-                                                      int64_t pair_base)
+                                                      int64_t pair_base, int wt)
 {
     int64_t mine = 0;
     uint64_t todo = __builtin_amdgcn_ballot_w64(heavy);
@@ -2216,7 +2229,7 @@ __device__ __forceinline__ int64_t emit_heavy_of_wave(EmitLds<SLOTS>* lds, bool 
         const int tl = __shfl((int)st.tiles0 | ((int)st.tiles1 << 16), src, 64);
         const int firsts = __shfl((int)st.first0 | ((int)st.first1 << 8), src, 64);
         const int64_t n = emit_pair_wave<WRITE, SLOTS>(lds, sp, so, mb, kb, packed & 0xFFFF, (packed >> 16) & 0xFF, (uint32_t)tl & 0xFFFFu,
-                                                        (uint32_t)tl >> 16, firsts & 0xFF, (firsts >> 8) & 0xFF, pairs, fusions, kept, masks, rec_offset, out, out_cap, pair_base);
+                                                        (uint32_t)tl >> 16, firsts & 0xFF, (firsts >> 8) & 0xFF, pairs, fusions, kept, masks, rec_offset, out, out_cap, pair_base, wt);
         if ((int)(threadIdx.x & 63) == src) mine = n;
     }
     return mine;
@@ -2243,7 +2256,7 @@ __global__ __launch_bounds__(EMIT_BLOCK) void k_emit_counted(const dsa_pair* __r
     // Pairs with more kept rows than the register path takes come in runs (a repeat in one fusion's window gives all its
     // reads the same ties): handing them to the whole wave one after the other (emit_pair_wave) would serialise a run
     // that sits in one wave, so here they stay with their lanes and walk global memory.
-    if (mine) emit_pair<true, EMIT_SLOTS_COUNTED>(&lds, p, o, st, pairs, fusions, kept, tasks, masks, rec_offset, out, out_cap, pair_base);
+    if (mine) emit_pair<true, EMIT_SLOTS_COUNTED>(&lds, p, o, st, pairs, fusions, kept, tasks, masks, rec_offset, out, out_cap, pair_base, g.wt);
 }
 
 // K4b: the other pairs - every one of them has a task in the generic replay's list, and the lane that finds the pair's
@@ -2276,8 +2289,8 @@ __global__ __launch_bounds__(EMIT_BLOCK) void k_emit_listed(const uint2* __restr
         const bool heavy = mine && emit_is_heavy<EMIT_SLOTS_LISTED>(st);
         DiagClock clk;
         int64_t n = 0;
-        if (mine && !heavy) n = emit_pair<WRITE, EMIT_SLOTS_LISTED>(&lds, p, o, st, pairs, fusions, kept, tasks, masks, rec_offset, out, out_cap, pair_base);
-        const int64_t nh = emit_heavy_of_wave<WRITE, EMIT_SLOTS_LISTED>(&lds, heavy, p, o, st, pairs, fusions, kept, masks, rec_offset, out, out_cap, pair_base);
+        if (mine && !heavy) n = emit_pair<WRITE, EMIT_SLOTS_LISTED>(&lds, p, o, st, pairs, fusions, kept, tasks, masks, rec_offset, out, out_cap, pair_base, g.wt);
+        const int64_t nh = emit_heavy_of_wave<WRITE, EMIT_SLOTS_LISTED>(&lds, heavy, p, o, st, pairs, fusions, kept, masks, rec_offset, out, out_cap, pair_base, g.wt);
         if (!WRITE && mine) rec_count[o] = heavy ? nh : n;
         if (!WRITE && mine)        // slowest lane: cycles << 24 | n_kept << 8 | n_tasks
             DSA_STAT_MAX(g, DS_SLOWEST_LISTED, (clk.lap() << 24) | ((unsigned long long)st.n_kept << 8) | st.n_tasks);

@@ -19,7 +19,7 @@ RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("fusion_id", "frag", "read_end", "
                                              "ref_second", "read_first", "read_second", "score", "pair_idx")])
 assert FUSION_DTYPE.itemsize == 20 and PAIR_DTYPE.itemsize == 20 and RECORD_DTYPE.itemsize == 40
 
-EXPORTS = ["dsa_create", "dsa_destroy", "dsa_get_limits", "dsa_last_error", "dsa_version", "dsa_build_flags", "dsa_device_count", "dsa_pick_device", "dsa_pick_device_among", "dsa_set_plan_options", "dsa_set_scratch_budget", "dsa_share_scratch", "dsa_align_batch",
+EXPORTS = ["dsa_create", "dsa_destroy", "dsa_get_limits", "dsa_tile_cols_for", "dsa_tile_cols_in_use", "dsa_last_error", "dsa_version", "dsa_build_flags", "dsa_device_count", "dsa_pick_device", "dsa_pick_device_among", "dsa_set_plan_options", "dsa_set_scratch_budget", "dsa_share_scratch", "dsa_align_batch",
            "dsa_upload", "dsa_plan", "dsa_run", "dsa_download", "dsa_copy_records_device", "dsa_get_timing", "dsa_get_kernel_counts", "dsa_set_stream", "dsa_synchronize",
            "dsa_stream_create", "dsa_stream_destroy", "dsa_stream_submit", "dsa_stream_collect", "dsa_stream_recollect", "dsa_stream_last_error",
            "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister"]
@@ -69,6 +69,8 @@ def load_library():
         lib.dsa_destroy.argtypes = [vp]
         lib.dsa_destroy.restype = None
         lib.dsa_get_limits.argtypes = [vp, ctypes.POINTER(Limits)]
+        lib.dsa_tile_cols_for.argtypes = [i32]
+        lib.dsa_tile_cols_in_use.argtypes = [vp]
         lib.dsa_last_error.argtypes = [vp]
         lib.dsa_last_error.restype = ctypes.c_char_p
         lib.dsa_version.restype = ctypes.c_char_p
@@ -104,6 +106,11 @@ def load_library():
         lib.dsa_host_unregister.argtypes = [vp]
         _lib = lib
     return _lib
+
+
+def tile_cols_for(max_window):
+    """dsa_tile_cols_for: the tile width in use for an upload whose widest window has max_window bases (no device needed)."""
+    return int(load_library().dsa_tile_cols_for(int(max_window)))
 
 
 def _check_arrays(ref_bytes, fusions, read_bytes, pairs):
@@ -144,6 +151,10 @@ class Context:
         lim = Limits()
         self.lib.dsa_get_limits(self.h, ctypes.byref(lim))
         return lim
+
+    def tile_cols_in_use(self):
+        """dsa_tile_cols_in_use: the tile width the resident upload is swept with."""
+        return int(self.lib.dsa_tile_cols_in_use(self.h))
 
     def set_plan_options(self, flags):
         """dsa_set_plan_options: PLAN_NO_* bits; effective from the next upload() / plan()."""

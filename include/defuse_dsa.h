@@ -80,7 +80,7 @@ typedef struct dsa_record {
 typedef struct dsa_limits {
     int32_t max_read_len;         /* longest read the DP kernels accept                          */
     int32_t max_ref_len;          /* longest reference window                                    */
-    int32_t tile_cols;            /* DP tile width (reference columns per register tile)         */
+    int32_t tile_cols;            /* widest DP tile (reference columns per register tile)        */
 } dsa_limits;
 
 /* Timings of the most recent dsa_run / dsa_align_batch, measured with HIP events on the ctx stream. */
@@ -118,6 +118,11 @@ int  dsa_create(dsa_ctx** out, int device);     /* device = HIP ordinal; fails (
 void dsa_destroy(dsa_ctx* ctx);
 int  dsa_get_limits(const dsa_ctx* ctx, dsa_limits* out);
 const char* dsa_last_error(const dsa_ctx* ctx); /* human-readable text for the last failure      */
+/* The tile width in use: an upload is swept in tiles of 64 columns or fewer, the built width for which its widest window
+ * pads out to the fewest swept columns (389 bases: seven tiles of 56).  dsa_tile_cols_for is that choice for a widest
+ * window of max_window bases (pure arithmetic, needs no device); dsa_tile_cols_in_use is the width of the resident upload. */
+int  dsa_tile_cols_for(int32_t max_window);
+int  dsa_tile_cols_in_use(const dsa_ctx* ctx);
 const char* dsa_version(void);                 /* "... src <hash of the sources and of the flags actually used>" */
 /* "sched=<iterative-ilp|default> <compiler flags>": the instruction scheduler the split-read kernels were built with (a
  * compiler that lacks the flag still builds the library, with a slower fill kernel and another source hash). */
