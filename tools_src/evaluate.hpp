@@ -74,27 +74,36 @@ inline void append_double(std::string& buf, double x)          // operator<<(dou
 
 struct EvalTexts { std::string seq, brk, pred; };
 
-// Evaluate (tools/SplitAlignment.cpp:484-594) of one group of alignments (one fusion id) and WriteSequence / WriteBreak /
-// WriteAlignments (:596-624) appended to out.  kept and splitScore are scratch.
-inline void EvaluateGroup(const SplitAlignmentTask& task, const std::vector<SplitAlignment>& alignments, EvalTexts& out,
-                          std::vector<const SplitAlignment*>& kept, std::map<std::pair<int, int>, int>& splitScore)
+// One kept alignment's terms of the two averages (tools/SplitAlignment.cpp:571-587), added in the caller's order.
+inline void AddSplitStats(int left, int right, double& posSum, double& minSum)
 {
-    const int fusionID = alignments.front().fusionID;
-    splitScore.clear();
-    for (const SplitAlignment& a : alignments) splitScore[a.refSplit] += a.score;
-    int maxScore = -1;
+    const double posRange = (double)(left + right - 2 * minAnchor);
+    const double posValue = std::max(0, left - minAnchor);
+    const double minRange = std::floor(0.5 * (double)(left + right - 2 * minAnchor));
+    const double minValue = std::max(0, std::min(left - minAnchor, right - minAnchor));
+    posSum += posValue / posRange;
+    minSum += minValue / minRange;
+}
+
+// What Evaluate decides for one group: the best split, its support and the two sums over the kept alignments.
+struct GroupVerdict {
+    bool found = false;                 // false: "Unable to find max score split"
     std::pair<int, int> best;
-    for (const auto& kv : splitScore)
-        if (kv.second > maxScore) { best = kv.first; maxScore = kv.second; }
+    int count = 0;
+    double posSum = 0.0, minSum = 0.0;
+};
+
+// The part of Evaluate after the arithmetic (tools/SplitAlignment.cpp:532-594) and WriteSequence / WriteBreak (:596-615):
+// the two DebugChecks, sequence assembly, break positions and the %g averages, appended to out.seq and out.brk.
+inline void WriteVerdict(const SplitAlignmentTask& task, int fusionID, const GroupVerdict& v, EvalTexts& out)
+{
     std::string sequence = "N";
     int breakPos[2] = {0, 0}, count = 0;
     double posAvg = -1.0, minAvg = -1.0;
-    kept.clear();
-    if (maxScore == -1) {
+    if (!v.found) {
         std::cerr << "Error: Unable to find max score split" << std::endl;
     } else {
-        for (const SplitAlignment& a : alignments)
-            if (a.refSplit == best) kept.push_back(&a);
+        const std::pair<int, int>& best = v.best;
         if (!(best.first <= (int)task.mSplitAlignSeq[0].length())) debug_check_failed("bestSplit.first <= mSplitAlignSeq[0].length()");
         if (!(best.second + 1 < (int)task.mSplitAlignSeq[1].length())) debug_check_failed("bestSplit.second + 1 < mSplitAlignSeq[1].length()");
         sequence.assign(task.mSplitRemainderSeq[0].sv());
@@ -106,19 +115,9 @@ inline void EvaluateGroup(const SplitAlignmentTask& task, const std::vector<Spli
                                                              : task.mSplitAlignSeqStart[0] + task.mSplitAlignSeqLength[0] - best.first;
         breakPos[1] = task.mSplitSeqStrand[1] == PlusStrand ? task.mSplitAlignSeqStart[1] + best.second + 1
                                                              : task.mSplitAlignSeqStart[1] + task.mSplitAlignSeqLength[1] - best.second - 2;
-        double posSum = 0.0, minSum = 0.0;
-        for (const SplitAlignment* a : kept) {
-            const int left = a->readSplit.first, right = a->readSplit.second;
-            const double posRange = (double)(left + right - 2 * minAnchor);
-            const double posValue = std::max(0, left - minAnchor);
-            const double minRange = std::floor(0.5 * (double)(left + right - 2 * minAnchor));
-            const double minValue = std::max(0, std::min(left - minAnchor, right - minAnchor));
-            posSum += posValue / posRange;
-            minSum += minValue / minRange;
-        }
-        count = (int)kept.size();
-        posAvg = posSum / (double)kept.size();
-        minAvg = minSum / kept.size();
+        count = v.count;
+        posAvg = v.posSum / (double)(size_t)v.count;
+        minAvg = v.minSum / (size_t)v.count;
     }
     append_int(out.seq, fusionID);
     out.seq += '\t'; out.seq += sequence; out.seq += "\t0\t";
@@ -134,6 +133,29 @@ inline void EvaluateGroup(const SplitAlignmentTask& task, const std::vector<Spli
         append_int(out.brk, breakPos[ce]);
         out.brk += '\n';
     }
+}
+
+// Evaluate (tools/SplitAlignment.cpp:484-594) of one group of alignments (one fusion id) and WriteSequence / WriteBreak /
+// WriteAlignments (:596-624) appended to out.  kept and splitScore are scratch.
+inline void EvaluateGroup(const SplitAlignmentTask& task, const std::vector<SplitAlignment>& alignments, EvalTexts& out,
+                          std::vector<const SplitAlignment*>& kept, std::map<std::pair<int, int>, int>& splitScore)
+{
+    const int fusionID = alignments.front().fusionID;
+    splitScore.clear();
+    for (const SplitAlignment& a : alignments) splitScore[a.refSplit] += a.score;
+    int maxScore = -1;
+    GroupVerdict v;
+    for (const auto& kv : splitScore)
+        if (kv.second > maxScore) { v.best = kv.first; maxScore = kv.second; }
+    kept.clear();
+    if (maxScore != -1) {
+        v.found = true;
+        for (const SplitAlignment& a : alignments)
+            if (a.refSplit == v.best) kept.push_back(&a);
+        for (const SplitAlignment* a : kept) AddSplitStats(a->readSplit.first, a->readSplit.second, v.posSum, v.minSum);
+        v.count = (int)kept.size();
+    }
+    WriteVerdict(task, fusionID, v, out);
     for (const SplitAlignment* a : kept) a->Write(out.pred);
 }
 
