@@ -46,11 +46,11 @@ struct HostResult {            // pinned: filled by k_publish at the end of a sl
 };
 
 struct PipeLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[7] = {};      // 0 pack start, 4 pack end, 1 fill start, 2 fill end, 3 phase-1 end, 5 emit start, 6 emit end
-    hipStream_t aux = nullptr;  // the two emit kernels of a slice run side by side: fork to aux, join back
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    HostResult* host = nullptr;
+    hipStream_t stream = nullptr;   // not owned: LaneSet::own[l], or for lane 0 the caller's stream (dsa_set_stream)
+    hiphost::Event ev[7];       // 0 pack start, 4 pack end, 1 fill start, 2 fill end, 3 phase-1 end, 5 emit start, 6 emit end
+    hiphost::Stream aux;        // the two emit kernels of a slice run side by side: fork to aux, join back
+    hiphost::Event ev_fork, ev_join;
+    hiphost::PinnedHost<HostResult> host;
     int slice = -1;             // slice whose phase 1 is in flight
     int64_t resident_upload = -1;   // the descriptors of (resident_upload, resident_slice) are on the device
     int resident_slice = -1;
@@ -76,13 +76,6 @@ struct PipeLane {
 #ifdef DSA_PRUNE_STATS
     DevBuf<unsigned long long> d_stats;
 #endif
-    void release()
-    {
-        d_wg_tier.release(); d_rowcodes.release(); d_rowbytes.release();
-        d_bnd.release(); d_cmax.release(); d_rmax.release(); d_tmask.release(); d_state.release(); d_kept.release();
-        d_rec_count.release(); d_rec_offset.release(); d_tasks.release(); d_masks.release(); d_gtasks.release();
-        d_ctr.release(); d_scan_tmp.release(); d_tstop.release();
-    }
 };
 
 // The two pipeline lanes of a context: streams, events, pinned result words and all per-slice scratch planes.  Contexts that
@@ -90,23 +83,12 @@ struct PipeLane {
 // (dsa_share_scratch), so the scratch is paid once.
 struct LaneSet {
     int device = -1;
-    hipStream_t own[2] = {};     // the lanes' private streams (lane 0 may run on a caller's stream instead)
+    hiphost::Stream own[2];      // the lanes' private streams (lane 0 may run on a caller's stream instead)
     PipeLane lane[2];
-    ~LaneSet()
+    ~LaneSet()                   // the members free themselves after this: the device must be theirs and idle
     {
         if (device >= 0) (void)hipSetDevice(device);
         (void)hipDeviceSynchronize();
-        for (PipeLane& L : lane) {
-            L.release();
-            for (auto& e : L.ev)
-                if (e) (void)hipEventDestroy(e);
-            if (L.ev_fork) (void)hipEventDestroy(L.ev_fork);
-            if (L.ev_join) (void)hipEventDestroy(L.ev_join);
-            if (L.aux) (void)hipStreamDestroy(L.aux);
-            if (L.host) (void)hipHostFree(L.host);
-        }
-        for (hipStream_t st : own)
-            if (st) (void)hipStreamDestroy(st);
     }
 };
 
@@ -139,7 +121,7 @@ struct dsa_ctx {
     int wt = W;                      // tile width in use of the upload (dsa_tile.hpp): picked for its widest window
     int nch_all = 1;                 // tiles (of wt columns) of the widest window of the upload: refcodes stride = nch_all * W
     DevBuf<uint32_t> d_refcodes;     // packed once per run for the whole upload
-    hipEvent_t ev_pack[2] = {};      // around k_pack_refs
+    hiphost::Event ev_pack[2];       // around k_pack_refs
     DevBuf<int32_t> d_orig;          // sweep order -> caller's pair index (Geom::orig)
     DevBuf<dsa_pair> d_pairs_in;     // the pairs in the caller's order, as uploaded
     DevBuf<dsa_pair> d_pairs;        // the pairs in sweep order, with the per-pair score bound in the padding bytes (k_plan_permute)
@@ -152,7 +134,7 @@ struct dsa_ctx {
     DevBuf<uint8_t> plan_flip, plan_sort_tmp;
     DevBuf<PlanGlobals> plan_glob;   // one per slice
     PlanParams plan_prm{};
-    hipEvent_t ev_plan[2] = {};      // around the planning kernels
+    hiphost::Event ev_plan[2];       // around the planning kernels
     bool plan_timed = false;         // ev_plan was recorded since the last run read it
     std::vector<Slice> slices;
     float last_plan_ms = 0.f;        // device time of the latest planning (upload's or dsa_plan's)
@@ -177,6 +159,14 @@ struct dsa_ctx {
 
     dsa_timing timing{};
     dsa_kernel_counts kcounts{};     // which kernels swept the last run (dsa_get_kernel_counts)
+
+    // The members free themselves after this (the last context of a shared set frees the lanes: streams, events, scratch
+    // planes), on the context's device and with nothing in flight: an emit of a lane may still be writing d_records.
+    ~dsa_ctx()
+    {
+        if (device >= 0) (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
 };
 
 hipStream_t dsa_ctx::main_stream() const { return lanes->lane[0].stream; }
@@ -229,12 +219,7 @@ void make_slices(dsa_ctx* ctx, int64_t n_pairs, int lqmax)
     const int lq1 = (lqmax + 1 + 3) & ~3;          // row planes are stored four rows per 16-byte word
     const size_t per_wg = slice_scratch_bytes(WG_WAVES, lq1, ctx->nch_all);
     int64_t chunk = (int64_t)std::min<size_t>((size_t)1 << 40, ctx->scratch_budget / std::max<size_t>(per_wg, 1)) * WG_LANES;
-    // A batch that fits one slice runs as ONE fill launch.  Cutting it in two so that the latency-bound finish kernels of the
-    // first half run beside the fill of the second (DEFUSE_DSA_SPLIT_LARGE=1) measured +1..2 % aligns/s on BASELINE configs[1]
-    // with the two fills overlapping on the two lanes — which blurs the per-launch times the roofline is computed from — and
-    // -10 % with the fills serialised; four or eight slices lose as well.  So it stays off.
-    if (const char* e = getenv("DEFUSE_DSA_SPLIT_LARGE"))
-        if (atoi(e) != 0 && chunk >= n_pairs && n_pairs >= ((int64_t)1 << 19)) chunk = ((n_pairs + 1) / 2 + WG_LANES - 1) / WG_LANES * WG_LANES;
+    // (a batch that fits one slice runs as ONE fill launch: cutting it measured slower or equal)
     if (const char* e = getenv("DEFUSE_DSA_SLICE_PAIRS")) chunk = std::min<int64_t>(chunk, std::max<int64_t>(WG_LANES, atoll(e) / WG_LANES * WG_LANES));
     chunk = std::max<int64_t>(chunk, WG_LANES);
     for (int64_t b = 0; b < n_pairs; b += chunk) {
@@ -362,6 +347,12 @@ FinishBufs finish_bufs(PipeLane& L)
     return fb;
 }
 
+// a slice's records go behind those of the earlier slices, into room for cap_left of them
+EmitOut emit_out(dsa_ctx* ctx, PipeLane& L, const Slice& s, size_t cap_left)
+{
+    return EmitOut{L.d_rec_offset.p, ctx->d_records.p + ctx->n_records, (uint64_t)cap_left, s.pair_begin};
+}
+
 // the records of a slice, behind those of the earlier slices (ev[5]..ev[6] time it): the pairs counted in the fill
 // kernel's tail by a per-pair launch, the others through the generic replay's task list
 // The listed pairs' kernels map one list entry to a thread; blocks without entries and second rounds both cost (they are
@@ -373,31 +364,38 @@ unsigned listed_grid(const PipeLane& L, int64_t n_pairs)
     const uint64_t blocks = (expect + expect / 64 + EMIT_BLOCK - 1) / EMIT_BLOCK + 1;
     return (unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 16), 16384);
 }
+// the listed pairs' records (WRITE, into eo) or their counts (eo zeroed), and the same for the long pairs of the slice
+template <bool WRITE>
+void launch_listed(dsa_ctx* ctx, PipeLane& L, const Slice& s, hipStream_t st, const Geom& g, const EmitOut& eo)
+{
+    hipLaunchKernelGGL(k_emit_listed<WRITE>, dim3(listed_grid(L, g.n_pairs)), dim3(EMIT_BLOCK), 0, st, finish_bufs(L), ctx->d_pairs.p + s.pair_begin,
+                       ctx->d_fusions.p, eo, g);
+}
+template <bool WRITE>
+void launch_long_emit(dsa_ctx* ctx, PipeLane& L, const Slice& s, hipStream_t st, const EmitOut& eo)
+{
+    if (ctx->h_long.empty()) return;
+    hipLaunchKernelGGL(k_long_emit<WRITE>, dim3((unsigned)((ctx->h_long.size() + 63) / 64)), dim3(64), 0, st, ctx->d_long.p, ctx->d_long_state.p,
+                       (int)ctx->h_long.size(), ctx->d_long_work.p, ctx->d_long_bits.p, (int64_t)s.pair_begin, (int64_t)s.pair_end, L.d_rec_count.p,
+                       eo.rec_offset, eo.out, eo.out_cap);
+}
+
 void launch_emit(dsa_ctx* ctx, PipeLane& L, const Slice& s, size_t cap_left, bool record_start = true)
 {
     const int64_t np = s.g.n_pairs;
     Geom g = s.g;
     g.tiers_launched = L.tiers_launched;
-    const dsa_pair* pairs = ctx->d_pairs.p + s.pair_begin;
-    dsa_record* out = ctx->d_records.p + ctx->n_records;
+    const EmitOut eo = emit_out(ctx, L, s, cap_left);
     L.emit_from = record_start ? 5 : 2;
     if (record_start) (void)hipEventRecord(L.ev[5], L.stream);      // (every event between two kernels is a gap of a few microseconds)
     // the listed pairs' kernel is a few latency-bound waves, the counted pairs' one streams: side by side
     (void)hipEventRecord(L.ev_fork, L.stream);
     (void)hipStreamWaitEvent(L.aux, L.ev_fork, 0);
-    hipLaunchKernelGGL(k_emit_listed<true>, dim3(listed_grid(L, np)), dim3(EMIT_BLOCK), 0, L.aux, L.d_gtasks.p, (uint64_t)L.d_gtasks.cap, L.d_ctr.p,
-                       pairs, ctx->d_fusions.p, L.d_state.p, L.d_kept.p, L.d_tasks.p, (uint64_t)L.d_tasks.cap, L.d_masks.p,
-                       (uint64_t)(L.d_masks.cap / 2), (uint64_t)L.d_kept.cap, L.d_rec_count.p, (const int64_t*)L.d_rec_offset.p, out,
-                       (uint64_t)cap_left, (int64_t)s.pair_begin, g);
+    launch_listed<true>(ctx, L, s, L.aux, g, eo);
     (void)hipEventRecord(L.ev_join, L.aux);
-    hipLaunchKernelGGL(k_emit_counted, dim3((unsigned)((np + EMIT_BLOCK - 1) / EMIT_BLOCK)), dim3(EMIT_BLOCK), 0, L.stream, pairs, ctx->d_fusions.p,
-                       L.d_state.p, L.d_kept.p, L.d_tasks.p, L.d_masks.p, (const int64_t*)L.d_rec_offset.p, out, (uint64_t)cap_left,
-                       (int64_t)s.pair_begin, L.d_ctr.p, (uint64_t)L.d_kept.cap, (uint64_t)L.d_tasks.cap, (uint64_t)(L.d_masks.cap / 2),
-                       (uint64_t)L.d_gtasks.cap, g);
-    if (!ctx->h_long.empty())
-        hipLaunchKernelGGL(k_long_emit<true>, dim3((unsigned)((ctx->h_long.size() + 63) / 64)), dim3(64), 0, L.stream, ctx->d_long.p, ctx->d_long_state.p,
-                           (int)ctx->h_long.size(), ctx->d_long_work.p, ctx->d_long_bits.p, (int64_t)s.pair_begin, (int64_t)s.pair_end, L.d_rec_count.p,
-                           (const int64_t*)L.d_rec_offset.p, out, (uint64_t)cap_left);
+    hipLaunchKernelGGL(k_emit_counted, dim3(grid_of(np, EMIT_BLOCK)), dim3(EMIT_BLOCK), 0, L.stream, finish_bufs(L), ctx->d_pairs.p + s.pair_begin,
+                       ctx->d_fusions.p, eo, g);
+    launch_long_emit<true>(ctx, L, s, L.stream, eo);
     (void)hipStreamWaitEvent(L.stream, L.ev_join, 0);
     (void)hipEventRecord(L.ev[6], L.stream);
 }
@@ -453,17 +451,9 @@ int launch_compute(dsa_ctx* ctx, PipeLane& L, const Slice& s)
     });
     if (!launched) return fail(ctx, DSA_E_DEVICE, "internal: no fill kernel for tile width %d", g.wt);
     HIPC(hipEventRecord(L.ev[2], st));
-    hipLaunchKernelGGL(k_replay, dim3(2048), dim3(REPLAY_BLOCK), 0, st, L.d_tasks.p, (uint64_t)L.d_tasks.cap, L.d_gtasks.p,
-                       (uint64_t)L.d_gtasks.cap, L.d_ctr.p, L.d_state.p, L.d_kept.p, (uint64_t)L.d_kept.cap, pairs, ctx->d_fusions.p,
-                       ctx->d_refcodes.p, L.d_rowcodes.p, L.d_bnd.p, L.d_tstop.p, L.d_masks.p, (uint64_t)(L.d_masks.cap / 2), g);
-    hipLaunchKernelGGL(k_emit_listed<false>, dim3(listed_grid(L, np)), dim3(EMIT_BLOCK), 0, st, L.d_gtasks.p, (uint64_t)L.d_gtasks.cap, L.d_ctr.p,
-                       pairs, ctx->d_fusions.p, L.d_state.p, L.d_kept.p, L.d_tasks.p, (uint64_t)L.d_tasks.cap, L.d_masks.p,
-                       (uint64_t)(L.d_masks.cap / 2), (uint64_t)L.d_kept.cap, L.d_rec_count.p, (const int64_t*)nullptr, (dsa_record*)nullptr,
-                       (uint64_t)0, (int64_t)s.pair_begin, g);
-    if (!ctx->h_long.empty())           // the long pairs of this slice: their counts replace the zeros of the blanked copies
-        hipLaunchKernelGGL(k_long_emit<false>, dim3((unsigned)((ctx->h_long.size() + 63) / 64)), dim3(64), 0, st, ctx->d_long.p, ctx->d_long_state.p,
-                           (int)ctx->h_long.size(), ctx->d_long_work.p, ctx->d_long_bits.p, (int64_t)s.pair_begin, (int64_t)s.pair_end, L.d_rec_count.p,
-                           (const int64_t*)nullptr, (dsa_record*)nullptr, (uint64_t)0);
+    hipLaunchKernelGGL(k_replay, dim3(2048), dim3(REPLAY_BLOCK), 0, st, fb, pairs, ctx->d_fusions.p, ctx->d_refcodes.p, L.d_rowcodes.p, L.d_bnd.p, g);
+    launch_listed<false>(ctx, L, s, st, g, EmitOut{});
+    launch_long_emit<false>(ctx, L, s, st, EmitOut{});      // the long pairs of this slice: their counts replace the zeros of the blanked copies
     if (int rc = exclusive_scan(ctx, L, L.d_rec_count.p, L.d_rec_offset.p, np + 1)) return rc;
     // the cursors and the record total go to the lane's pinned result words
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, L.d_ctr.p, L.d_rec_offset.p + np, reinterpret_cast<const unsigned long long*>(ctx->plan_glob.p + (&s - ctx->slices.data())),
@@ -536,7 +526,8 @@ int phase2(dsa_ctx* ctx, PipeLane& L)
         const bool tiers_ok = (c.need_tiers & ~L.tiers_launched) == 0;
         L.tier_hint = tiers_ok ? c.need_tiers : 0xFu;          // what the next slice of this lane launches
         if (!tiers_ok) ctx->kcounts.slices_rerun += 1;
-        if (tiers_ok && c.n_kept <= L.d_kept.cap && c.n_tasks <= L.d_tasks.cap && c.n_masks <= L.d_masks.cap / 2 && c.n_gtasks <= L.d_gtasks.cap) break;
+        const FinishBufs fb = finish_bufs(L);
+        if (tiers_ok && c.n_kept <= fb.kept_cap && c.n_tasks <= fb.task_cap && c.n_masks <= fb.mask_cap && c.n_gtasks <= fb.gtask_cap) break;
         if (attempt >= 3) return fail(ctx, DSA_E_DEVICE, "finish stage did not converge");
         HIPC(L.d_kept.reserve(c.n_kept + 1024));
         HIPC(L.d_tasks.reserve(c.n_tasks + 1024));
@@ -685,17 +676,17 @@ static int create_ctx(dsa_ctx** out, int device, dsa_ctx* share)
         ctx->lanes->device = device;
         for (int l = 0; l < 2; ++l) {
             PipeLane& L = ctx->lanes->lane[l];
-            ok = ok && hipStreamCreate(&ctx->lanes->own[l]) == hipSuccess;
+            ok = ok && ctx->lanes->own[l].create() == hipSuccess;
             L.stream = ctx->lanes->own[l];
-            for (auto& e : L.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-            ok = ok && hipStreamCreateWithFlags(&L.aux, hipStreamNonBlocking) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipHostMalloc((void**)&L.host, sizeof(HostResult)) == hipSuccess;
+            for (auto& e : L.ev) ok = ok && e.create() == hipSuccess;
+            ok = ok && L.aux.create(hipStreamNonBlocking) == hipSuccess;
+            ok = ok && L.ev_fork.create(hipEventDisableTiming) == hipSuccess;
+            ok = ok && L.ev_join.create(hipEventDisableTiming) == hipSuccess;
+            ok = ok && L.host.alloc() == hipSuccess;
         }
     }
-    for (auto& e : ctx->ev_pack) ok = ok && hipEventCreate(&e) == hipSuccess;
-    for (auto& e : ctx->ev_plan) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (auto& e : ctx->ev_pack) ok = ok && e.create() == hipSuccess;
+    for (auto& e : ctx->ev_plan) ok = ok && e.create() == hipSuccess;
     if (!ok) {
         dsa_destroy(ctx);
         return DSA_E_DEVICE;
@@ -711,25 +702,7 @@ static int create_ctx(dsa_ctx** out, int device, dsa_ctx* share)
 
 int dsa_create(dsa_ctx** out, int device) { return create_ctx(out, device, nullptr); }
 
-void dsa_destroy(dsa_ctx* ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
-    ctx->d_ref.release(); ctx->d_reads.release(); ctx->d_fusions.release(); ctx->d_pairs.release(); ctx->d_orig.release(); ctx->d_pairs_in.release();
-    ctx->d_min_score.release(); ctx->d_records.release(); ctx->d_refcodes.release();
-    ctx->plan_runs.release(); ctx->plan_key.release(); ctx->plan_key_sorted.release(); ctx->plan_fidx.release(); ctx->plan_order.release();
-    ctx->plan_bsum.release(); ctx->plan_start.release(); ctx->plan_rank.release(); ctx->plan_bound.release(); ctx->plan_flip.release();
-    ctx->plan_sort_tmp.release(); ctx->plan_glob.release();
-    ctx->d_long.release(); ctx->d_long_fusions.release(); ctx->d_long_work.release(); ctx->d_long_rows.release(); ctx->d_long_state.release();
-    ctx->d_long_bits.release();
-    for (auto& e : ctx->ev_pack)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_plan)
-        if (e) (void)hipEventDestroy(e);
-    ctx->lanes.reset();          // the last context of a shared set frees the lanes (streams, events, scratch planes)
-    delete ctx;
-}
+void dsa_destroy(dsa_ctx* ctx) { delete ctx; }       // ~dsa_ctx selects the device and waits for it first
 
 int dsa_share_scratch(dsa_ctx* ctx, dsa_ctx* donor)
 {
@@ -763,7 +736,7 @@ int dsa_set_stream(dsa_ctx* ctx, void* hip_stream)
 {
     if (!ctx) return DSA_E_ARG;
     ctx->user_stream = (hipStream_t)hip_stream;
-    ctx->lanes->lane[0].stream = hip_stream ? (hipStream_t)hip_stream : ctx->lanes->own[0];      // lane 1 keeps its private stream
+    ctx->lanes->lane[0].stream = hip_stream ? (hipStream_t)hip_stream : ctx->lanes->own[0].s;      // lane 1 keeps its private stream
     return DSA_OK;
 }
 
@@ -1130,9 +1103,9 @@ int dsa_align_batch(dsa_ctx* ctx, const uint8_t* ref_bytes, int64_t ref_bytes_le
 struct dsa_stream {
     int device = -1, depth = 0;
     std::vector<dsa_ctx*> slot;
-    hipStream_t s_in = nullptr, s_out = nullptr;
+    hiphost::Stream s_in, s_out;
     struct Job {
-        hipEvent_t ev_in = nullptr, ev_out = nullptr;
+        hiphost::Event ev_in, ev_out;
         dsa_record* out = nullptr;
         int64_t out_cap = 0, n = 0;
         int rc = 0;
@@ -1206,18 +1179,18 @@ int dsa_stream_create(dsa_stream** out, int device, int depth)
     dsa_stream* s = new dsa_stream();
     s->device = device;
     s->depth = depth;
-    s->job.resize(depth);
+    s->job = std::vector<dsa_stream::Job>((size_t)depth);       // (built in place: a Job owns its events and does not move)
     bool ok = true;
     for (int k = 0; k < depth && ok; ++k) {
         dsa_ctx* c = nullptr;
         ok = create_ctx(&c, device, k > 0 ? s->slot[0] : nullptr) == DSA_OK;       // the slots share slot 0's pipeline lanes
         if (ok) s->slot.push_back(c);
     }
-    ok = ok && hipStreamCreateWithFlags(&s->s_in, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && s->s_in.create(hipStreamNonBlocking) == hipSuccess;
+    ok = ok && s->s_out.create(hipStreamNonBlocking) == hipSuccess;
     for (auto& j : s->job) {
-        ok = ok && hipEventCreateWithFlags(&j.ev_in, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&j.ev_out, hipEventDisableTiming) == hipSuccess;
+        ok = ok && j.ev_in.create(hipEventDisableTiming) == hipSuccess;
+        ok = ok && j.ev_out.create(hipEventDisableTiming) == hipSuccess;
     }
     if (!ok) {
         dsa_stream_destroy(s);
@@ -1241,14 +1214,8 @@ void dsa_stream_destroy(dsa_stream* s)
     }
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    for (auto& j : s->job) {
-        if (j.ev_in) (void)hipEventDestroy(j.ev_in);
-        if (j.ev_out) (void)hipEventDestroy(j.ev_out);
-    }
-    if (s->s_in) (void)hipStreamDestroy(s->s_in);
-    if (s->s_out) (void)hipStreamDestroy(s->s_out);
     for (size_t k = s->slot.size(); k-- > 0;) dsa_destroy(s->slot[k]);
-    delete s;
+    delete s;                                   // the copy streams and the jobs' events
 }
 
 const char* dsa_stream_last_error(const dsa_stream* s) { return s ? s->err.c_str() : "no stream"; }

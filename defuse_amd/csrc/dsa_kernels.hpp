@@ -484,7 +484,7 @@ __device__ __forceinline__ int nth_set_bit(uint64_t m, int n)   // index of the 
 // the (M1 tile, M2 tile) the tables will be built for.
 constexpr int TMASK_TILES = 16;   // tmask covers references of at most 16 tiles
 
-// device buffers of the finish stage, handed to the fill kernels as one argument
+// device buffers of the finish stage and their capacities, handed to the fill and the finish kernels as one argument
 struct FinishBufs {
     PairState* state;
     KeptRow* kept;
@@ -496,6 +496,27 @@ struct FinishBufs {
     int32_t* tstop;        // [wave][tile]: row groups of the tile whose bnd / cmax were stored (the rest is dead)
     int64_t* rec_count;    // [pair in the caller's order]: records of the pair
 };
+
+// where the emit kernels write a slice's records (all zero for the launch that only counts them)
+struct EmitOut {
+    const int64_t* rec_offset;   // [pair in the caller's order]: exclusive sum of FinishBufs::rec_count
+    dsa_record* out;             // the slice's first record
+    uint64_t out_cap;            // room behind out, in records
+    int64_t pair_base;           // the slice's first pair in the caller's order
+};
+
+// The slice's counts are void: a finish buffer overflowed (the cursors ran past a capacity), or some workgroups were not swept
+// because their fill kernel was not launched and their pairs have no state yet.  The finish kernels return at once and the
+// host runs the slice again (phase2).
+__device__ __forceinline__ bool finish_void(const FinishBufs& fb, const Geom& g)
+{
+    const Counters* __restrict__ ctr = fb.ctr;
+    return ctr->n_tasks > fb.task_cap || ctr->n_masks > fb.mask_cap || ctr->n_kept > fb.kept_cap || ctr->n_gtasks > fb.gtask_cap ||
+           (ctr->need_tiers & ~g.tiers_launched) != 0;
+}
+
+// one side's 64 columns of a {M1 mask, M2 mask} pair
+__device__ __forceinline__ uint64_t mask_half(const uint4& v, int h) { return h ? ((uint64_t)v.w << 32) | v.z : ((uint64_t)v.y << 32) | v.x; }
 
 // tstop is read in the kernel that writes it, by other lanes and waves of the workgroup: bypass the
 // vector L1, whose lines may predate the store
@@ -1737,26 +1758,25 @@ __device__ __forceinline__ uint32_t equal_columns_quarter(const uint32_t (&X)[RW
     return acc;
 }
 
-__global__ __launch_bounds__(REPLAY_BLOCK, 5) void k_replay(const ReplayTask* __restrict__ tasks, uint64_t task_cap,
-                                                   const uint2* __restrict__ gtasks, uint64_t gtask_cap,
-                                                   const Counters* __restrict__ ctr,
-                                                   const PairState* __restrict__ state,
-                                                   const KeptRow* __restrict__ kept, uint64_t kept_cap,
-                                                   const dsa_pair* __restrict__ pairs,
+__global__ __launch_bounds__(REPLAY_BLOCK, 5) void k_replay(FinishBufs fb, const dsa_pair* __restrict__ pairs,
                                                    const dsa_fusion* __restrict__ fusions,
                                                    const uint32_t* __restrict__ refcodes,
                                                    const uint32_t* __restrict__ rowcodes,
-                                                   const uint32_t* __restrict__ bnd, const int32_t* __restrict__ tstop,
-                                                   uint64_t* __restrict__ masks, uint64_t mask_cap, Geom g)
+                                                   const uint32_t* __restrict__ bnd, Geom g)
 {
+    const ReplayTask* __restrict__ tasks = fb.tasks;
+    const uint2* __restrict__ gtasks = fb.gtasks;
+    const PairState* __restrict__ state = fb.state;
+    const KeptRow* __restrict__ kept = fb.kept;
+    const int32_t* __restrict__ tstop = fb.tstop;
+    uint64_t* __restrict__ masks = fb.masks;
     __shared__ int s_hist[258];
     __shared__ unsigned short s_order[REPLAY_TASKS];
     __shared__ ReplayTask s_task[REPLAY_TASKS];
     __shared__ uint64_t s_kc[KCACHE * REPLAY_BLOCK];   // the first kept rows of every lane's pair: the cursors advance without a global load
     static_assert(REPLAY_BLOCK == WG_LANES, "kept_row() strides the cache by WG_LANES");
-    const unsigned long long n_g = ctr->n_gtasks;
-    if (ctr->n_tasks > task_cap || ctr->n_masks > mask_cap || ctr->n_kept > kept_cap || n_g > gtask_cap) return;
-    if (ctr->need_tiers & ~g.tiers_launched) return;      // some workgroups were not swept: the host runs the slice again with every fill kernel
+    const unsigned long long n_g = fb.ctr->n_gtasks;
+    if (finish_void(fb, g)) return;
     const int q = threadIdx.x & (RQ - 1);             // quarter of the tile
     const int slot = threadIdx.x / RQ;                // task slot of the block
     for (unsigned long long base = (unsigned long long)blockIdx.x * REPLAY_TASKS; base < n_g;
@@ -1834,12 +1854,11 @@ __global__ __launch_bounds__(REPLAY_BLOCK, 5) void k_replay(const ReplayTask* __
         const int stop0 = c0 > 0 ? tstop[w * g.nch + (c0 - 1)] : 0;   // stored row groups of the tiles to the left
         const int stop1 = c1 > 0 ? tstop[w * g.nch + (c1 - 1)] : 0;
         // the planes hold four rows per 16-byte word: row j of this pair is word (j / 4) * 64 + lane, element j % 4
-        auto plane_at = [&](int j) -> int64_t { return ((int64_t)(j >> 2) * WAVE + lane) * 4 + (j & 3); };
-        auto row_code = [&](int j) -> uint32_t { return rows[plane_at(j < 0 ? 0 : j > R ? R : j)]; };
+        auto row_code = [&](int j) -> uint32_t { return rows[rowidx(j < 0 ? 0 : j > R ? R : j, lane)]; };
         auto boundary = [&](int j) -> uint32_t {          // quarter 0 only: the tiles to the left (V = 0 past their stop)
             const int jj = j < 0 ? 0 : j > R ? R : j;
-            const uint32_t x0 = (jj >> 2) < stop0 ? bi0[plane_at(jj)] : BIAS2;
-            const uint32_t x1 = (jj >> 2) < stop1 ? bi1[plane_at(jj)] : BIAS2;
+            const uint32_t x0 = (jj >> 2) < stop0 ? bi0[rowidx(jj, lane)] : BIAS2;
+            const uint32_t x1 = (jj >> 2) < stop1 ? bi1[rowidx(jj, lane)] : BIAS2;
             return (x0 & 0xFFFFu) | (x1 & 0xFFFF0000u);
         };
         int Rw = R;                                        // the wave steps as long as its longest task
@@ -1923,14 +1942,31 @@ __global__ void k_publish(const Counters* __restrict__ ctr, const int64_t* __res
 // K4: emit.  For every kept split a (ascending) the cross product columns1 x columns2 in ascending
 // order (tools/SplitReadAligner.cpp:233-269), then the refSplit de-duplication of
 // tools/SplitAlignment.cpp:381-391 (first occurrence wins).  WRITE=false counts.
-__device__ __forceinline__ bool col_in(const ReplayTask* tasks, const uint64_t* masks, uint32_t tb, uint32_t te,
-                                       int k, int h, int col /*1-based matrix column*/, int wt)
+__device__ __forceinline__ bool col_in(const FinishBufs& fb, uint32_t tb, uint32_t te, int k, int h, int col /*1-based matrix column*/, int wt)
 {
+    const ReplayTask* __restrict__ tasks = fb.tasks;
+    const uint64_t* __restrict__ masks = fb.masks;
     const int c = (col - 1) / wt, bit = (col - 1) % wt;
     for (uint32_t q = tb; q < te; ++q)
         if ((h ? tasks[q].chunk1 : tasks[q].chunk0) == c)
             return (masks[((uint64_t)tasks[q].mask_begin + k) * 2 + h] >> bit) & 1ull;
     return false;
+}
+
+// One record of a pair: `rec` holds what the pair's records share (read_second = the read's length), (i1, i2) are the
+// matrix columns, kr the kept split.  40-byte records at a multiple of 40 bytes from a 256-byte aligned base: five 8-byte stores
+__device__ __forceinline__ void store_record(dsa_record* __restrict__ dst_rec, const dsa_record& rec, int ref1_len, int i1, int i2, const KeptRow& kr)
+{
+    dsa_record r = rec;
+    r.ref_first = i1;
+    r.ref_second = ref1_len - i2 - 1;
+    r.read_first = kr.a;
+    r.read_second = rec.read_second - kr.a;
+    r.score = kr.m1 < kr.m2 ? kr.m1 : kr.m2;
+    uint2* dst = reinterpret_cast<uint2*>(dst_rec);
+    const uint2* src = reinterpret_cast<const uint2*>(&r);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) dst[q] = src[q];
 }
 
 constexpr int EMIT_BLOCK = 128;
@@ -1946,12 +1982,14 @@ struct EmitLds {
 
 // The records of one pair (WRITE) or their number.  wt = Geom::wt: bit b of a mask of tile c is matrix column c * wt + b + 1.
 template <bool WRITE, int SLOTS>
-__device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int64_t o, const PairState& st, const dsa_pair* __restrict__ pairs,
-                                             const dsa_fusion* __restrict__ fusions, const KeptRow* __restrict__ kept,
-                                             const ReplayTask* __restrict__ tasks, const uint64_t* __restrict__ masks,
-                                             const int64_t* __restrict__ rec_offset, dsa_record* __restrict__ out, uint64_t out_cap,
-                                             int64_t pair_base, int wt)
+__device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int64_t o, const PairState& st, const FinishBufs& fb,
+                                             const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions, const EmitOut& eo, int wt)
 {
+    const KeptRow* __restrict__ kept = fb.kept;
+    const ReplayTask* __restrict__ tasks = fb.tasks;
+    const uint64_t* __restrict__ masks = fb.masks;
+    const int64_t* __restrict__ rec_offset = eo.rec_offset;
+    dsa_record* __restrict__ out = eo.out;
     const int tid = threadIdx.x;
     int64_t n = 0;
     int64_t wr = 0;
@@ -1962,29 +2000,17 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
         wr = rec_offset[o];
         const int64_t wr_end = rec_offset[o + 1];
         const dsa_fusion fu = fusions[pr.fusion_idx];
-        if ((uint64_t)wr_end > out_cap) return 0;    // host grows the buffer and reruns emit
+        if ((uint64_t)wr_end > eo.out_cap) return 0; // host grows the buffer and reruns emit
         rec.fusion_id = fu.fusion_id;
         rec.frag = pr.frag;
         rec.read_end = pr.read_end;
         rec.revcomp = pr.revcomp;
         rec.read_second = pr.read_len;               // minus a below
-        rec.pair_idx = (int32_t)(pair_base + o);
+        rec.pair_idx = (int32_t)(eo.pair_base + o);
         ref1_len = fu.ref1_len;
     }
-    // 40-byte records at a multiple of 40 bytes from a 256-byte aligned base: five 8-byte stores
     auto put = [&](int i1, int i2, const KeptRow& kr) {
-        if (WRITE) {
-            dsa_record r = rec;
-            r.ref_first = i1;
-            r.ref_second = ref1_len - i2 - 1;
-            r.read_first = kr.a;
-            r.read_second = rec.read_second - kr.a;
-            r.score = kr.m1 < kr.m2 ? kr.m1 : kr.m2;
-            uint2* dst = reinterpret_cast<uint2*>(out + wr);
-            const uint2* src = reinterpret_cast<const uint2*>(&r);
-#pragma unroll
-            for (int q = 0; q < 5; ++q) dst[q] = src[q];
-        }
+        if (WRITE) store_record(out + wr, rec, ref1_len, i1, i2, kr);
         ++wr;
         ++n;
     };
@@ -2015,19 +2041,17 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
         }
         const bool both = st.tiles0 != 0 && st.tiles1 != 0;
         const int base1 = __builtin_ctz(st.tiles0 | 0x10000u) * wt + 1, base2 = __builtin_ctz(st.tiles1 | 0x10000u) * wt + 1;
-        auto lo64 = [](const uint4& v) -> uint64_t { return ((uint64_t)v.y << 32) | v.x; };
-        auto hi64 = [](const uint4& v) -> uint64_t { return ((uint64_t)v.w << 32) | v.z; };
 #pragma unroll
         for (int k = 0; k < EMIT_REG_ROWS; ++k) {
             if (both && k < K) {
                 const KeptRow kr = __builtin_bit_cast(KeptRow, kr2[k]);
-                for (uint64_t r1 = lo64(m[k]); r1; r1 &= r1 - 1) {
+                for (uint64_t r1 = mask_half(m[k], 0); r1; r1 &= r1 - 1) {
                     const int b1 = __builtin_ctzll(r1);
-                    for (uint64_t r2 = hi64(m[k]); r2; r2 &= r2 - 1) {
+                    for (uint64_t r2 = mask_half(m[k], 1); r2; r2 &= r2 - 1) {
                         const int b2 = __builtin_ctzll(r2);
                         bool dup = false;     // same refSplit <=> same (i1,i2) at an earlier kept a
 #pragma unroll
-                        for (int k2 = 0; k2 < k; ++k2) dup = dup || (((lo64(m[k2]) >> b1) & 1ull) && ((hi64(m[k2]) >> b2) & 1ull));
+                        for (int k2 = 0; k2 < k; ++k2) dup = dup || (((mask_half(m[k2], 0) >> b1) & 1ull) && ((mask_half(m[k2], 1) >> b2) & 1ull));
                         if (!dup) put(base1 + b1, base2 + b2, kr);
                     }
                 }
@@ -2055,10 +2079,7 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
             }
         }
         // pairs with more masks than a lane stages (and that no wave took) walk global memory
-        auto mask_of = [&](int k, int t, int h) -> uint64_t {
-            const uint4 v = staged ? lds->mask[t * K + k][tid] : masks4[t * K + k];
-            return h ? ((uint64_t)v.w << 32) | v.z : ((uint64_t)v.y << 32) | v.x;
-        };
+        auto mask_of = [&](int k, int t, int h) -> uint64_t { return mask_half(staged ? lds->mask[t * K + k][tid] : masks4[t * K + k], h); };
         for (int k = 0; k < K; ++k) {
             const KeptRow kr = __builtin_bit_cast(KeptRow, staged ? lds->kept[k][tid] : kept2[k]);
             for (uint32_t w0 = st.tiles0; w0; w0 &= w0 - 1) {
@@ -2083,20 +2104,22 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
         for (int k = 0; k < K; ++k) {
             const KeptRow kr = kept[st.kept_begin + k];
             for (uint32_t q1 = tb; q1 < te; ++q1) {        // tasks hold M1 tiles in ascending order
-                if (tasks[q1].chunk0 == NO_CHUNK) continue;
+                const int c1 = tasks[q1].chunk0;           // (read once: nothing tells the compiler that put() leaves the tasks alone)
+                if (c1 == NO_CHUNK) continue;
                 uint64_t m1 = masks[((uint64_t)tasks[q1].mask_begin + k) * 2];
                 while (m1) {
-                    const int i1 = tasks[q1].chunk0 * wt + __builtin_ctzll(m1) + 1;
+                    const int i1 = c1 * wt + __builtin_ctzll(m1) + 1;
                     m1 &= m1 - 1;
                     for (uint32_t q2 = tb; q2 < te; ++q2) {
-                        if (tasks[q2].chunk1 == NO_CHUNK) continue;
+                        const int c2 = tasks[q2].chunk1;
+                        if (c2 == NO_CHUNK) continue;
                         uint64_t m2 = masks[((uint64_t)tasks[q2].mask_begin + k) * 2 + 1];
                         while (m2) {
-                            const int i2 = tasks[q2].chunk1 * wt + __builtin_ctzll(m2) + 1;
+                            const int i2 = c2 * wt + __builtin_ctzll(m2) + 1;
                             m2 &= m2 - 1;
                             bool dup = false;     // same refSplit <=> same (i1,i2) at an earlier kept a
                             for (int k2 = 0; k2 < k && !dup; ++k2)
-                                dup = col_in(tasks, masks, tb, te, k2, 0, i1, wt) && col_in(tasks, masks, tb, te, k2, 1, i2, wt);
+                                dup = col_in(fb, tb, te, k2, 0, i1, wt) && col_in(fb, tb, te, k2, 1, i2, wt);
                             if (!dup) put(i1, i2, kr);
                         }
                     }
@@ -2112,33 +2135,33 @@ __device__ __forceinline__ int64_t emit_pair(EmitLds<SLOTS>* lds, int64_t p, int
 // counts kept row k (the de-dup only reads earlier rows' masks), a prefix sum places the rows, and every lane writes
 // its row's records: the order is that of emit_pair.  Called by all 64 lanes with the same arguments.
 template <bool WRITE, int SLOTS>
-__device__ __forceinline__ int64_t emit_pair_wave(EmitLds<SLOTS>* lds, int64_t p, int64_t o, uint32_t mask_begin, uint32_t kept_begin, int K, int T,
-                                                  uint32_t tiles0, uint32_t tiles1, int first0, int first1, const dsa_pair* __restrict__ pairs,
-                                                  const dsa_fusion* __restrict__ fusions, const KeptRow* __restrict__ kept,
-                                                  const uint64_t* __restrict__ masks, const int64_t* __restrict__ rec_offset,
-                                                  dsa_record* __restrict__ out, uint64_t out_cap, int64_t pair_base, int wt)
+__device__ __forceinline__ int64_t emit_pair_wave(EmitLds<SLOTS>* lds, int64_t p, int64_t o, const PairState& st, const FinishBufs& fb,
+                                                  const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions, const EmitOut& eo, int wt)
 {
+    const KeptRow* __restrict__ kept = fb.kept;
+    const uint64_t* __restrict__ masks = fb.masks;
+    const int64_t* __restrict__ rec_offset = eo.rec_offset;
+    dsa_record* __restrict__ out = eo.out;
+    const uint32_t tiles0 = st.tiles0, tiles1 = st.tiles1;
+    const int K = st.n_kept, T = st.n_tasks, first0 = st.first0, first1 = st.first1;
     const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
     auto slot_m = [&](int e) -> uint4& { return lds->mask[e >> 6][wbase + (e & 63)]; };
     auto slot_k = [&](int e) -> uint2& { return lds->kept[e >> 6][wbase + (e & 63)]; };
-    const uint4* masks4 = reinterpret_cast<const uint4*>(masks) + mask_begin;
-    const uint2* kept2 = reinterpret_cast<const uint2*>(kept) + kept_begin;
+    const uint4* masks4 = reinterpret_cast<const uint4*>(masks) + st.mask_begin;
+    const uint2* kept2 = reinterpret_cast<const uint2*>(kept) + st.kept_begin;
     __builtin_amdgcn_wave_barrier();
     for (int e = lane; e < K * T; e += 64) slot_m(e) = masks4[e];
     for (int e = lane; e < K; e += 64) slot_k(e) = kept2[e];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    auto mask_of = [&](int k, int t, int h) -> uint64_t {
-        const uint4 v = slot_m(t * K + k);
-        return h ? ((uint64_t)v.w << 32) | v.z : ((uint64_t)v.y << 32) | v.x;
-    };
+    auto mask_of = [&](int k, int t, int h) -> uint64_t { return mask_half(slot_m(t * K + k), h); };
     int64_t wr = 0;
     dsa_record rec = {};
     int ref1_len = 0;
     if (WRITE) {
         wr = rec_offset[o];
-        if ((uint64_t)rec_offset[o + 1] > out_cap) return 0;   // uniform: host grows the buffer and reruns emit
+        if ((uint64_t)rec_offset[o + 1] > eo.out_cap) return 0;   // uniform: host grows the buffer and reruns emit
         const dsa_pair pr = pairs[p];
         const dsa_fusion fu = fusions[pr.fusion_idx];
         rec.fusion_id = fu.fusion_id;
@@ -2146,7 +2169,7 @@ __device__ __forceinline__ int64_t emit_pair_wave(EmitLds<SLOTS>* lds, int64_t p
         rec.read_end = pr.read_end;
         rec.revcomp = pr.revcomp;
         rec.read_second = pr.read_len;
-        rec.pair_idx = (int32_t)(pair_base + o);
+        rec.pair_idx = (int32_t)(eo.pair_base + o);
         ref1_len = fu.ref1_len;
     }
     // the records of kept row k, handed to fn(i1, i2) in output order
@@ -2181,19 +2204,7 @@ __device__ __forceinline__ int64_t emit_pair_wave(EmitLds<SLOTS>* lds, int64_t p
         if (WRITE && k < K) {
             const KeptRow kr = __builtin_bit_cast(KeptRow, slot_k(k));
             int64_t at = wr + total + (incl - n_row);
-            row(k, [&](int i1, int i2) {
-                dsa_record r = rec;
-                r.ref_first = i1;
-                r.ref_second = ref1_len - i2 - 1;
-                r.read_first = kr.a;
-                r.read_second = rec.read_second - kr.a;
-                r.score = kr.m1 < kr.m2 ? kr.m1 : kr.m2;
-                uint2* dst = reinterpret_cast<uint2*>(out + at);
-                const uint2* src = reinterpret_cast<const uint2*>(&r);
-#pragma unroll
-                for (int q = 0; q < 5; ++q) dst[q] = src[q];
-                ++at;
-            });
+            row(k, [&](int i1, int i2) { store_record(out + at++, rec, ref1_len, i1, i2, kr); });
         }
         total += __shfl(incl, 63, 64);
     }
@@ -2212,11 +2223,8 @@ __device__ __forceinline__ bool emit_is_heavy(const PairState& st)
 
 // the heavy pairs of a wave, one after the other; fn_done(lane's own pair result) is told the count of the lane's pair
 template <bool WRITE, int SLOTS>
-__device__ __forceinline__ int64_t emit_heavy_of_wave(EmitLds<SLOTS>* lds, bool heavy, int64_t p, int64_t o, const PairState& st,
-                                                      const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions,
-                                                      const KeptRow* __restrict__ kept, const uint64_t* __restrict__ masks,
-                                                      const int64_t* __restrict__ rec_offset, dsa_record* __restrict__ out, uint64_t out_cap,
-                                                      int64_t pair_base, int wt)
+__device__ __forceinline__ int64_t emit_heavy_of_wave(EmitLds<SLOTS>* lds, bool heavy, int64_t p, int64_t o, const PairState& st, const FinishBufs& fb,
+                                                      const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions, const EmitOut& eo, int wt)
 {
     int64_t mine = 0;
     uint64_t todo = __builtin_amdgcn_ballot_w64(heavy);
@@ -2224,27 +2232,23 @@ __device__ __forceinline__ int64_t emit_heavy_of_wave(EmitLds<SLOTS>* lds, bool 
         const int src = __builtin_ctzll(todo);
         todo &= todo - 1;
         const int64_t sp = __shfl((int)p, src, 64), so = __shfl((int)o, src, 64);       // pair indices are below 2^31
-        const uint32_t mb = (uint32_t)__shfl((int)st.mask_begin, src, 64), kb = (uint32_t)__shfl((int)st.kept_begin, src, 64);
-        const int packed = __shfl((int)st.n_kept | ((int)st.n_tasks << 16), src, 64);
-        const int tl = __shfl((int)st.tiles0 | ((int)st.tiles1 << 16), src, 64);
-        const int firsts = __shfl((int)st.first0 | ((int)st.first1 << 8), src, 64);
-        const int64_t n = emit_pair_wave<WRITE, SLOTS>(lds, sp, so, mb, kb, packed & 0xFFFF, (packed >> 16) & 0xFF, (uint32_t)tl & 0xFFFFu,
-                                                        (uint32_t)tl >> 16, firsts & 0xFF, (firsts >> 8) & 0xFF, pairs, fusions, kept, masks, rec_offset, out, out_cap, pair_base, wt);
+        struct Words { int w[sizeof(PairState) / 4]; } v = __builtin_bit_cast(Words, st);      // the source lane's pair
+#pragma unroll
+        for (int& x : v.w) x = __shfl(x, src, 64);
+        const PairState sst = __builtin_bit_cast(PairState, v);
+        const int64_t n = emit_pair_wave<WRITE, SLOTS>(lds, sp, so, sst, fb, pairs, fusions, eo, wt);
         if ((int)(threadIdx.x & 63) == src) mine = n;
     }
     return mine;
 }
 
 // K4a: the records of the pairs the fill kernel's tail has counted (one tile pair, replayed there) - one lane per pair.
-__global__ __launch_bounds__(EMIT_BLOCK) void k_emit_counted(const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions,
-                       const PairState* __restrict__ state, const KeptRow* __restrict__ kept,
-                       const ReplayTask* __restrict__ tasks, const uint64_t* __restrict__ masks,
-                       const int64_t* __restrict__ rec_offset, dsa_record* __restrict__ out, uint64_t out_cap, int64_t pair_base,
-                       const Counters* __restrict__ ctr, uint64_t kept_cap, uint64_t task_cap, uint64_t mask_cap, uint64_t gtask_cap, Geom g)
+__global__ __launch_bounds__(EMIT_BLOCK) void k_emit_counted(FinishBufs fb, const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions,
+                                                               EmitOut eo, Geom g)
 {
     __shared__ EmitLds<EMIT_SLOTS_COUNTED> lds;
-    if (ctr->n_tasks > task_cap || ctr->n_masks > mask_cap || ctr->n_kept > kept_cap || ctr->n_gtasks > gtask_cap) return;   // counts are void: the host reruns the slice
-    if (ctr->need_tiers & ~g.tiers_launched) return;      // pairs of workgroups that were not swept have no state yet
+    const PairState* __restrict__ state = fb.state;
+    if (finish_void(fb, g)) return;
     const int64_t p = (int64_t)blockIdx.x * EMIT_BLOCK + threadIdx.x;
     PairState st = {};
     int64_t o = 0;                                   // records are counted and written in the caller's pair order
@@ -2256,24 +2260,22 @@ __global__ __launch_bounds__(EMIT_BLOCK) void k_emit_counted(const dsa_pair* __r
     // Pairs with more kept rows than the register path takes come in runs (a repeat in one fusion's window gives all its
     // reads the same ties): handing them to the whole wave one after the other (emit_pair_wave) would serialise a run
     // that sits in one wave, so here they stay with their lanes and walk global memory.
-    if (mine) emit_pair<true, EMIT_SLOTS_COUNTED>(&lds, p, o, st, pairs, fusions, kept, tasks, masks, rec_offset, out, out_cap, pair_base, g.wt);
+    if (mine) emit_pair<true, EMIT_SLOTS_COUNTED>(&lds, p, o, st, fb, pairs, fusions, eo, g.wt);
 }
 
 // K4b: the other pairs - every one of them has a task in the generic replay's list, and the lane that finds the pair's
 // first such task there counts (WRITE = false) or writes the pair's records.  These lanes all work through several
 // tiles, which one lane in ten of a per-pair launch would do while the rest of its wave waits.
 template <bool WRITE>
-__global__ __launch_bounds__(EMIT_BLOCK) void k_emit_listed(const uint2* __restrict__ gtasks, uint64_t gtask_cap, const Counters* __restrict__ ctr,
-                       const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions,
-                       const PairState* __restrict__ state, const KeptRow* __restrict__ kept,
-                       const ReplayTask* __restrict__ tasks, uint64_t task_cap, const uint64_t* __restrict__ masks, uint64_t mask_cap,
-                       uint64_t kept_cap, int64_t* __restrict__ rec_count, const int64_t* __restrict__ rec_offset,
-                       dsa_record* __restrict__ out, uint64_t out_cap, int64_t pair_base, Geom g)
+__global__ __launch_bounds__(EMIT_BLOCK) void k_emit_listed(FinishBufs fb, const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions,
+                                                              EmitOut eo, Geom g)
 {
     __shared__ EmitLds<EMIT_SLOTS_LISTED> lds;
-    const unsigned long long n_g = ctr->n_gtasks;
-    if (ctr->n_tasks > task_cap || ctr->n_masks > mask_cap || ctr->n_kept > kept_cap || n_g > gtask_cap) return;   // the host reruns the slice
-    if (ctr->need_tiers & ~g.tiers_launched) return;
+    const uint2* __restrict__ gtasks = fb.gtasks;
+    const PairState* __restrict__ state = fb.state;
+    int64_t* __restrict__ rec_count = fb.rec_count;
+    const unsigned long long n_g = fb.ctr->n_gtasks;
+    if (finish_void(fb, g)) return;
     // Consecutive list entries go to different blocks (entry = thread * blocks + block within a round of the grid): the
     // pairs with many kept rows come in runs, and a wave takes its heavy pairs one after the other.
     const unsigned long long stride = (unsigned long long)gridDim.x * EMIT_BLOCK;
@@ -2289,8 +2291,8 @@ __global__ __launch_bounds__(EMIT_BLOCK) void k_emit_listed(const uint2* __restr
         const bool heavy = mine && emit_is_heavy<EMIT_SLOTS_LISTED>(st);
         DiagClock clk;
         int64_t n = 0;
-        if (mine && !heavy) n = emit_pair<WRITE, EMIT_SLOTS_LISTED>(&lds, p, o, st, pairs, fusions, kept, tasks, masks, rec_offset, out, out_cap, pair_base, g.wt);
-        const int64_t nh = emit_heavy_of_wave<WRITE, EMIT_SLOTS_LISTED>(&lds, heavy, p, o, st, pairs, fusions, kept, masks, rec_offset, out, out_cap, pair_base, g.wt);
+        if (mine && !heavy) n = emit_pair<WRITE, EMIT_SLOTS_LISTED>(&lds, p, o, st, fb, pairs, fusions, eo, g.wt);
+        const int64_t nh = emit_heavy_of_wave<WRITE, EMIT_SLOTS_LISTED>(&lds, heavy, p, o, st, fb, pairs, fusions, eo, g.wt);
         if (!WRITE && mine) rec_count[o] = heavy ? nh : n;
         if (!WRITE && mine)        // slowest lane: cycles << 24 | n_kept << 8 | n_tasks
             DSA_STAT_MAX(g, DS_SLOWEST_LISTED, (clk.lap() << 24) | ((unsigned long long)st.n_kept << 8) | st.n_tasks);

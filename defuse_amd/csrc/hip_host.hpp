@@ -96,7 +96,7 @@ struct Event {
     Event(const Event&) = delete;
     Event& operator=(const Event&) = delete;
     ~Event() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create() { return hipEventCreate(&e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
     operator hipEvent_t() const { return e; }
 };
 
@@ -108,6 +108,18 @@ struct Stream {
     ~Stream() { if (s) (void)hipStreamDestroy(s); }
     hipError_t create(unsigned flags = hipStreamDefault) { return hipStreamCreateWithFlags(&s, flags); }
     operator hipStream_t() const { return s; }
+};
+
+// One T in pinned host memory, which kernels store results into and the host reads after a synchronise.
+template <typename T>
+struct PinnedHost {
+    T* p = nullptr;
+    PinnedHost() = default;
+    PinnedHost(const PinnedHost&) = delete;
+    PinnedHost& operator=(const PinnedHost&) = delete;
+    ~PinnedHost() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc() { return hipHostMalloc((void**)&p, sizeof(T)); }
+    T* operator->() const { return p; }
 };
 
 // hipcub's two-call protocol: run(nullptr, bytes) asks for the temp size, tmp grows to it if it has to, run(tmp.p, bytes)

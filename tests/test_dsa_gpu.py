@@ -51,6 +51,34 @@ def test_parity_many_tiles_paths(gpu_ctx, ora):
     assert len(got) > 3
 
 
+def test_parity_many_tiles_ties_across_rows_and_tiles(gpu_ctx, ora):
+    """Windows of more than 16 tiles (emit walks the task list) whose pairs tie across kept rows AND across tiles, so that the
+    de-duplication there (col_in: the same columns at an earlier kept split, looked up in another task's mask) decides records.
+    The junction J ends in the 6 bases ref1 starts with, so a read that leaves ref0 6 bases before J's end can split at 7
+    places; J stands twice in ref0, 446 bases apart, so every split has two columns, in different tiles."""
+    rng = np.random.default_rng(7)
+    bb = cases.BatchBuilder()
+    for _ in range(2):
+        shared = cases.rnd(rng, 6)
+        J = cases.rnd(rng, 40) + shared
+        ref0 = cases.rnd(rng, 300) + J + cases.rnd(rng, 400) + J + cases.rnd(rng, 300)
+        ref1 = shared + cases.rnd(rng, 1100)
+        assert len(ref0) == 1092
+        f = bb.add_fusion(ref0, ref1)
+        for _ in range(32):
+            a = int(rng.integers(12, 40))
+            bb.add_read(f, J[len(J) - 6 - a:len(J) - 6] + ref1[:60 - a])
+    batch = bb.arrays()
+    exp = ora.align_batch(*batch)
+    for p in range(len(batch[3])):              # from the oracle: no pair passes without ties of both kinds
+        mine = exp[exp["pair_idx"] == p]
+        assert len(np.unique(mine["read_first"])) >= 2, p
+        assert len(np.unique(mine["ref_first"] // 64)) >= 2, p
+    got = gpu_ctx.align_batch(*batch)
+    assert len(got) == len(exp), (len(got), len(exp))
+    assert got.tobytes() == exp.tobytes()
+
+
 def test_parity_single_fusion_fast_path(gpu_ctx, ora):
     """One fusion, many reads over {A,C,G,T,N}: every workgroup takes the LDS-table kernels."""
     import numpy as np
