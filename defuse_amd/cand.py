@@ -59,6 +59,8 @@ def _bind(lib):
     lib.cand_session_destroy.argtypes = [p]
     lib.cand_session_destroy.restype = None
     lib.cand_enumerate.argtypes = [p, p, i64, i32, p, i64, ctypes.POINTER(i64), ctypes.POINTER(CandTiming)]
+    lib.cand_enumerate_device.argtypes = [p, p, i64, i32, ctypes.POINTER(i64), ctypes.POINTER(CandTiming)]      # (declared in defuse_bat.h)
+    lib.cand_records_device.argtypes = [p, ctypes.POINTER(p), ctypes.POINTER(i64)]
     lib.cand_last_error.restype = ctypes.c_char_p
     return lib
 
@@ -169,6 +171,20 @@ class Session:
         if rc != 0 or n2 != n:
             _fail(self._lib, "cand_enumerate", rc)
         return out
+
+    def enumerate_device(self, als, order=ORDER_VISIT):
+        """cand_enumerate_device: the kept candidates stay in the session's device buffer.  Returns (device pointer, count)
+        from cand_records_device, valid until the next call on this session; the timing is in self.timing."""
+        a = np.ascontiguousarray(als, dtype=ALIGNMENT_DTYPE)
+        n = ctypes.c_int64()
+        rc = self._lib.cand_enumerate_device(self.handle, _ptr(a), len(a), order, ctypes.byref(n), ctypes.byref(self.timing))
+        if rc != 0:
+            _fail(self._lib, "cand_enumerate_device", rc)
+        dev, m = ctypes.c_void_p(), ctypes.c_int64()
+        rc = self._lib.cand_records_device(self.handle, ctypes.byref(dev), ctypes.byref(m))
+        if rc != 0 or m.value != n.value:
+            _fail(self._lib, "cand_records_device", rc)
+        return dev.value or 0, n.value
 
     def reset(self):
         rc = self._lib.cand_session_reset(self.handle)

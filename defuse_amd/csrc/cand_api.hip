@@ -24,6 +24,7 @@
 #include <climits>
 #include <string>
 
+#include "../../include/defuse_bat.h"      // cand_enumerate_device, cand_records_device
 #include "../../include/defuse_cand.h"
 #include "../../include/defuse_dsa.h"
 #include "hip_host.hpp"
@@ -267,6 +268,9 @@ struct cand_session {
     DeviceBuffer<uint32_t, GrowSize> flag, pos, rank, rank_sorted, keep_v, keep_s, kpos, fkey, fkey_sorted, idx, idx_sorted;
     DeviceBuffer<cand_record, GrowSize> rec, rec_sorted;
     DeviceBuffer<uint8_t, GrowSize> tmp;
+    // the records of the latest cand_enumerate_device (in rec or rec_sorted), until the next call on the session
+    const cand_record* resident = nullptr;
+    int64_t n_resident = 0;
 };
 
 namespace {
@@ -430,11 +434,22 @@ void cand_session_destroy(cand_session* s)
     delete s;
 }
 
-int cand_enumerate(cand_session* s, const cand_alignment* alignments, int64_t n, int32_t order, cand_record* out, int64_t cap,
-                   int64_t* n_out, cand_timing* timing)
+}  // extern "C"
+
+namespace {
+
+// cand_enumerate (RESIDENT = false: the records go to `out` if they fit cap) and cand_enumerate_device (true: they stay in
+// the session's buffer, nothing is downloaded and no capacity is asked for)
+template <bool RESIDENT>
+int enumerate(cand_session* s, const cand_alignment* alignments, int64_t n, int32_t order, cand_record* out, int64_t cap, int64_t* n_out,
+              cand_timing* timing)
 {
     if (!n_out) return CAND_FAIL(DSA_E_ARG, "cand_enumerate: no n_out");
     *n_out = 0;
+    if (s) {
+        s->resident = nullptr;
+        s->n_resident = 0;
+    }
     if (n < 0) return CAND_FAIL(DSA_E_ARG, "negative number of alignments (%lld)", (long long)n);
     if (n > (int64_t)INT32_MAX) return CAND_FAIL(DSA_E_LIMIT, "more than 2^31 - 1 alignments in one call");
     if (n && !alignments) return CAND_FAIL(DSA_E_ARG, "cand_enumerate: no alignments");
@@ -511,7 +526,7 @@ int cand_enumerate(cand_session* s, const cand_alignment* alignments, int64_t n,
     }
     *n_out = K;
     if (timing) { timing->n_hits = H; timing->n_visited = V; timing->n_kept = K; }
-    if (K > cap) return CAND_FAIL(DSA_E_CAPACITY, "%lld candidates, room for %lld", (long long)K, (long long)cap);   // the session is as it was
+    if (!RESIDENT && K > cap) return CAND_FAIL(DSA_E_CAPACITY, "%lld candidates, room for %lld", (long long)K, (long long)cap);   // the session is as it was
 
     if (K) {
         const unsigned gv = grid_of(V), gk = grid_of(K);
@@ -540,8 +555,12 @@ int cand_enumerate(cand_session* s, const cand_alignment* alignments, int64_t n,
         hipLaunchKernelGGL(k_cand_merge, dim3(grid_of(s->n_seen + K)), dim3(BLOCK), 0, st, (const u64*)s->seen.p, s->n_seen, (const u64*)s->new_keys.p, K,
                            s->seen_next.p);
         CAND_HIP(hipEventRecord(s->ev[2], st));
-        CAND_HIP(hipMemcpyAsync(out, result, (size_t)K * sizeof(cand_record), hipMemcpyDeviceToHost, st));
+        if (!RESIDENT) CAND_HIP(hipMemcpyAsync(out, result, (size_t)K * sizeof(cand_record), hipMemcpyDeviceToHost, st));
         CAND_HIP(hipEventRecord(s->ev[3], st));
+        if (RESIDENT) {
+            s->resident = result;
+            s->n_resident = K;
+        }
     } else {
         CAND_HIP(hipEventRecord(s->ev[2], st));
         CAND_HIP(hipEventRecord(s->ev[3], st));
@@ -556,8 +575,31 @@ int cand_enumerate(cand_session* s, const cand_alignment* alignments, int64_t n,
     if (timing) {
         timing->upload_ms = hiphost::elapsed(s->ev[0], s->ev[1]);
         timing->device_ms = hiphost::elapsed(s->ev[1], s->ev[2]);
-        timing->download_ms = hiphost::elapsed(s->ev[2], s->ev[3]);
+        timing->download_ms = RESIDENT ? 0.f : hiphost::elapsed(s->ev[2], s->ev[3]);
     }
+    return DSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cand_enumerate(cand_session* s, const cand_alignment* alignments, int64_t n, int32_t order, cand_record* out, int64_t cap,
+                   int64_t* n_out, cand_timing* timing)
+{
+    return enumerate<false>(s, alignments, n, order, out, cap, n_out, timing);
+}
+
+int cand_enumerate_device(cand_session* s, const cand_alignment* alignments, int64_t n, int32_t order, int64_t* n_out, cand_timing* timing)
+{
+    return enumerate<true>(s, alignments, n, order, nullptr, 0, n_out, timing);
+}
+
+int cand_records_device(const cand_session* s, const void** dev, int64_t* n)
+{
+    if (!s || !dev || !n) return CAND_FAIL(DSA_E_ARG, "cand_records_device: no %s", !s ? "session" : "output");
+    *dev = s->resident;
+    *n = s->n_resident;
     return DSA_OK;
 }
 

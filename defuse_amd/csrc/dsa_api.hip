@@ -99,6 +99,11 @@ struct Slice {                       // a contiguous range of the caller's pair 
     Geom g{};
 };
 
+struct UploadCheck {                 // what the validation kernel of dsa_upload_device leaves (k_upload_check)
+    unsigned long long bad_fusion, bad_pair;      // lowest offending index * 2 (+ 1: a limit, not an argument error); ~0: none
+    int maxwin, lqmax;
+};
+
 }  // namespace
 
 struct dsa_ctx {
@@ -149,6 +154,7 @@ struct dsa_ctx {
     DevBuf<uint32_t> d_long_bits;
     int64_t long_cells = 0;          // DP cells of the long pairs
     int64_t long_blank_cells = 0;    // what the planning counts for their blanked copies (an empty read on the blanked windows)
+    DevBuf<UploadCheck> d_upload_check;   // what k_upload_check found (dsa_upload_device)
 
     // per-slice scratch lives in two pipeline lanes so that the latency-bound finish stage of one
     // slice overlaps the fill of the next (separate HIP streams)
@@ -751,17 +757,54 @@ int dsa_synchronize(dsa_ctx* ctx)
 
 namespace {
 
-// validation, buffers, copies (queued on st) and slice geometry of an upload; the planning is queued by the caller
-int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64_t ref_bytes_len, const dsa_fusion* fusions,
-               int32_t n_fusions, const uint8_t* read_bytes, int64_t read_bytes_len, const dsa_pair* pairs,
-               int64_t n_pairs)
+// the four arrays of an upload, in host memory (dsa_upload) or in memory of the ctx's device (dsa_upload_device)
+struct UploadArrays {
+    const uint8_t* ref_bytes;
+    int64_t ref_bytes_len;
+    const dsa_fusion* fusions;
+    int32_t n_fusions;
+    const uint8_t* read_bytes;
+    int64_t read_bytes_len;
+    const dsa_pair* pairs;
+    int64_t n_pairs;
+};
+
+// what the validation of an upload finds out for its geometry
+struct UploadShape {
+    int maxwin = 0;     // widest window the tile kernels see
+    int lqmax = 0;      // longest read they see
+    int wt = W;         // tile width in use
+};
+
+int upload_check_sizes(dsa_ctx* ctx, const UploadArrays& a)
 {
-    if (!ctx) return DSA_E_ARG;
-    if (n_fusions < 0 || n_pairs < 0 || ref_bytes_len < 0 || read_bytes_len < 0)
+    if (a.n_fusions < 0 || a.n_pairs < 0 || a.ref_bytes_len < 0 || a.read_bytes_len < 0)
         return fail(ctx, DSA_E_ARG, "negative size");
-    if (n_pairs >= ((int64_t)1 << 31)) return fail(ctx, DSA_E_LIMIT, "more than 2^31-1 pairs in one batch");
-    if ((n_fusions && !fusions) || (n_pairs && !pairs) || (ref_bytes_len && !ref_bytes) || (read_bytes_len && !read_bytes))
+    if (a.n_pairs >= ((int64_t)1 << 31)) return fail(ctx, DSA_E_LIMIT, "more than 2^31-1 pairs in one batch");
+    if ((a.n_fusions && !a.fusions) || (a.n_pairs && !a.pairs) || (a.ref_bytes_len && !a.ref_bytes) || (a.read_bytes_len && !a.read_bytes))
         return fail(ctx, DSA_E_ARG, "null pointer with non-zero size");
+    return DSA_OK;
+}
+
+// the tile width in use follows the widest window the tile kernels see (DEFUSE_DSA_TILE_COLS: one of the built widths, for A/B runs)
+int upload_tile_width(dsa_ctx* ctx, int maxwin, int* wt)
+{
+    *wt = pick_tile_width(maxwin);
+    if (const char* e = getenv("DEFUSE_DSA_TILE_COLS")) {
+        if (!is_tile_width(atoi(e))) return fail(ctx, DSA_E_ARG, "DEFUSE_DSA_TILE_COLS=%s is not a built tile width", e);
+        *wt = atoi(e);
+    }
+    return DSA_OK;
+}
+
+// validation of host arrays; the pairs and fusions beyond the 16-bit kernels go to the context's work list of the 32-bit path
+int upload_validate_host(dsa_ctx* ctx, const UploadArrays& a, UploadShape* shape)
+{
+    const int64_t ref_bytes_len = a.ref_bytes_len, read_bytes_len = a.read_bytes_len, n_pairs = a.n_pairs;
+    const dsa_fusion* fusions = a.fusions;
+    const int32_t n_fusions = a.n_fusions;
+    const dsa_pair* pairs = a.pairs;
+    if (int rc = upload_check_sizes(ctx, a)) return rc;
     // A pair goes to the 16-bit tile kernels unless its read or one of its fusion's windows is too long for them; those few
     // are swept in 32 bits by kernels of their own (dsa_long.hpp), and the regular path sees them as empty reads / windows.
     ctx->h_long.clear();
@@ -782,13 +825,8 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
         }
         maxwin = std::max(maxwin, std::max(fu.ref0_len, fu.ref1_len));
     }
-    // the tile width in use follows the widest window the tile kernels see (DEFUSE_DSA_TILE_COLS: one of the built widths, for A/B runs)
-    int wt = pick_tile_width(maxwin);
-    if (const char* e = getenv("DEFUSE_DSA_TILE_COLS")) {
-        if (!is_tile_width(atoi(e))) return fail(ctx, DSA_E_ARG, "DEFUSE_DSA_TILE_COLS=%s is not a built tile width", e);
-        wt = atoi(e);
-    }
-    const int nch_all = std::max(1, tiles_of(maxwin, wt));
+    int wt = W;
+    if (int rc = upload_tile_width(ctx, maxwin, &wt)) return rc;
     const bool any_long_fusion = !ctx->h_long_fusions.empty();
     int lqmax = 0;
     for (int64_t p = 0; p < n_pairs; ++p) {
@@ -820,6 +858,25 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
         }
         lqmax = std::max(lqmax, (int)pr.read_len);
     }
+    shape->maxwin = maxwin;
+    shape->lqmax = lqmax;
+    shape->wt = wt;
+    return DSA_OK;
+}
+
+// The part every upload shares once its arrays are known to be good: the ctx's buffers, the copies into them (queued on st;
+// `kind` says where the arrays are), and the geometry that follows from the widest window and the longest read — tile width,
+// tiles of the widest window, min-score table, parameters of the planning kernels, slices.  The planning is queued by the caller.
+int upload_commit(dsa_ctx* ctx, hipStream_t st, const UploadArrays& a, hipMemcpyKind kind, const UploadShape& shape)
+{
+    const uint8_t* ref_bytes = a.ref_bytes;
+    const int64_t ref_bytes_len = a.ref_bytes_len, read_bytes_len = a.read_bytes_len, n_pairs = a.n_pairs;
+    const dsa_fusion* fusions = a.fusions;
+    const int32_t n_fusions = a.n_fusions;
+    const uint8_t* read_bytes = a.read_bytes;
+    const dsa_pair* pairs = a.pairs;
+    const int maxwin = shape.maxwin, lqmax = shape.lqmax, wt = shape.wt;
+    const int nch_all = std::max(1, tiles_of(maxwin, wt));
     HIPC(hipSetDevice(ctx->device));
     ctx->have_results = false;
     ctx->n_records = 0;
@@ -835,10 +892,10 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
     ctx->wt = wt;
     ctx->nch_all = nch_all;
     HIPC(ctx->d_refcodes.reserve((size_t)n_fusions * nch_all * W + 1));
-    if (ref_bytes_len) HIPC(hipMemcpyAsync(ctx->d_ref.p, ref_bytes, ref_bytes_len, hipMemcpyHostToDevice, st));
-    if (read_bytes_len) HIPC(hipMemcpyAsync(ctx->d_reads.p, read_bytes, read_bytes_len, hipMemcpyHostToDevice, st));
-    if (n_fusions) HIPC(hipMemcpyAsync(ctx->d_fusions.p, fusions, n_fusions * sizeof(dsa_fusion), hipMemcpyHostToDevice, st));
-    if (n_pairs) HIPC(hipMemcpyAsync(ctx->d_pairs_in.p, pairs, n_pairs * sizeof(dsa_pair), hipMemcpyHostToDevice, st));
+    if (ref_bytes_len) HIPC(hipMemcpyAsync(ctx->d_ref.p, ref_bytes, ref_bytes_len, kind, st));
+    if (read_bytes_len) HIPC(hipMemcpyAsync(ctx->d_reads.p, read_bytes, read_bytes_len, kind, st));
+    if (n_fusions) HIPC(hipMemcpyAsync(ctx->d_fusions.p, fusions, n_fusions * sizeof(dsa_fusion), kind, st));
+    if (n_pairs) HIPC(hipMemcpyAsync(ctx->d_pairs_in.p, pairs, n_pairs * sizeof(dsa_pair), kind, st));
     if (!ctx->h_long.empty() || !ctx->h_long_fusions.empty()) {
         const int nl = (int)ctx->h_long.size(), nlf = (int)ctx->h_long_fusions.size();
         HIPC(ctx->d_long.reserve((size_t)nl + 1));
@@ -870,6 +927,102 @@ int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64
     return DSA_OK;
 }
 
+// validation, buffers, copies (queued on st) and slice geometry of an upload from host arrays; the planning is queued by the caller
+int upload_enqueue(dsa_ctx* ctx, hipStream_t st, const uint8_t* ref_bytes, int64_t ref_bytes_len, const dsa_fusion* fusions,
+               int32_t n_fusions, const uint8_t* read_bytes, int64_t read_bytes_len, const dsa_pair* pairs,
+               int64_t n_pairs)
+{
+    if (!ctx) return DSA_E_ARG;
+    const UploadArrays a{ref_bytes, ref_bytes_len, fusions, n_fusions, read_bytes, read_bytes_len, pairs, n_pairs};
+    UploadShape shape;
+    if (int rc = upload_validate_host(ctx, a, &shape)) return rc;
+    return upload_commit(ctx, st, a, hipMemcpyHostToDevice, shape);
+}
+
+// What upload_validate_host finds in its two loops, found by one kernel over arrays that are on the device already.  A thread
+// checks fusion t and pair t as the host does; the lowest offending index of each kind is left by atomicMin (index * 2 + 1 for
+// a limit, + 0 for an argument error: of one index the argument error is the one the host reports), the widest window and the
+// longest read by a workgroup reduction and one atomicMax each.
+struct MaxOf {
+    __device__ int operator()(int x, int y) const { return x > y ? x : y; }
+};
+
+__global__ __launch_bounds__(256) void k_upload_check(const dsa_fusion* __restrict__ fusions, int32_t n_fusions, int64_t ref_bytes_len,
+                                                      const dsa_pair* __restrict__ pairs, int64_t n_pairs, int64_t read_bytes_len,
+                                                      UploadCheck* __restrict__ out)
+{
+    using Reduce = hipcub::BlockReduce<int, 256>;
+    __shared__ typename Reduce::TempStorage tmp_w, tmp_q;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int win = 0, lq = 0;
+    if (t < n_fusions) {
+        const dsa_fusion fu = fusions[t];
+        if (fu.ref0_len < 0 || fu.ref1_len < 0 || fu.ref0_off < 0 || fu.ref1_off < 0 || (int64_t)fu.ref0_off + fu.ref0_len > ref_bytes_len ||
+            (int64_t)fu.ref1_off + fu.ref1_len > ref_bytes_len)
+            atomicMin(&out->bad_fusion, (unsigned long long)t * 2);
+        else if (fu.ref0_len > FAST_MAX_REF || fu.ref1_len > FAST_MAX_REF)
+            atomicMin(&out->bad_fusion, (unsigned long long)t * 2 + 1);
+        else
+            win = max(fu.ref0_len, fu.ref1_len);
+    }
+    if (t < n_pairs) {
+        const dsa_pair pr = pairs[t];
+        if (pr.fusion_idx < 0 || pr.fusion_idx >= n_fusions || pr.read_len < 0 || pr.read_off < 0 || (int64_t)pr.read_off + pr.read_len > read_bytes_len)
+            atomicMin(&out->bad_pair, (unsigned long long)t * 2);
+        else if (pr.read_len > FAST_MAX_READ)
+            atomicMin(&out->bad_pair, (unsigned long long)t * 2 + 1);
+        else
+            lq = pr.read_len;
+    }
+    win = Reduce(tmp_w).Reduce(win, MaxOf());
+    lq = Reduce(tmp_q).Reduce(lq, MaxOf());
+    if (threadIdx.x == 0) {
+        if (win > 0) atomicMax(&out->maxwin, win);
+        if (lq > 0) atomicMax(&out->lqmax, lq);
+    }
+}
+
+// validation of arrays in device memory: one kernel, one small copy back.  The 32-bit path builds its work list from host
+// arrays, so a read or a window beyond the 16-bit kernels is refused here.
+int upload_validate_device(dsa_ctx* ctx, hipStream_t st, const UploadArrays& a, UploadShape* shape)
+{
+    if (int rc = upload_check_sizes(ctx, a)) return rc;
+    HIPC(hipSetDevice(ctx->device));
+    UploadCheck res{~0ull, ~0ull, 0, 0};
+    const int64_t n = std::max<int64_t>(a.n_fusions, a.n_pairs);
+    if (n) {
+        HIPC(ctx->d_upload_check.reserve(1));
+        HIPC(hipMemcpyAsync(ctx->d_upload_check.p, &res, sizeof res, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_upload_check, dim3(grid_of(n)), dim3(256), 0, st, a.fusions, a.n_fusions, a.ref_bytes_len, a.pairs, a.n_pairs, a.read_bytes_len,
+                           ctx->d_upload_check.p);
+        HIPC(hipMemcpyAsync(&res, ctx->d_upload_check.p, sizeof res, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        HIPC(hipGetLastError());
+    }
+    // what the host entry does at the same points, in its order: the fusions, the tile width, the pairs
+    ctx->h_long.clear();
+    ctx->h_long_fusions.clear();
+    ctx->long_cells = 0;
+    ctx->long_blank_cells = 0;
+    if (res.bad_fusion != ~0ull) {
+        const int f = (int)(res.bad_fusion >> 1);
+        if (res.bad_fusion & 1)
+            return fail(ctx, DSA_E_LIMIT, "fusion %d: reference window longer than %d, the range of the 16-bit kernels: such an upload goes through dsa_upload", f, FAST_MAX_REF);
+        return fail(ctx, DSA_E_ARG, "fusion %d: reference window outside ref_bytes", f);
+    }
+    shape->maxwin = res.maxwin;
+    if (int rc = upload_tile_width(ctx, shape->maxwin, &shape->wt)) return rc;
+    if (res.bad_pair != ~0ull) {
+        const long long p = (long long)(res.bad_pair >> 1);
+        if (res.bad_pair & 1)
+            return fail(ctx, DSA_E_LIMIT, "pair %lld: read longer than %d, the range of the 16-bit kernels: such an upload goes through dsa_upload", p, FAST_MAX_READ);
+        // (the host entry tells a bad fusion_idx from a read outside read_bytes; both are DSA_E_ARG of the same pair)
+        return fail(ctx, DSA_E_ARG, "pair %lld: bad fusion_idx or read outside read_bytes", p);
+    }
+    shape->lqmax = res.lqmax;
+    return DSA_OK;
+}
+
 
 }  // namespace
 
@@ -883,6 +1036,21 @@ int dsa_upload(dsa_ctx* ctx, const uint8_t* ref_bytes, int64_t ref_bytes_len, co
     if (int rc = upload_enqueue(ctx, ctx->main_stream(), ref_bytes, ref_bytes_len, fusions, n_fusions, read_bytes, read_bytes_len, pairs, n_pairs)) return rc;
     if (int rc = enqueue_plan(ctx)) return rc;
     HIPC(hipStreamSynchronize(ctx->main_stream()));    // the caller's buffers are free again when dsa_upload returns
+    HIPC(hipGetLastError());
+    return DSA_OK;
+}
+
+int dsa_upload_device(dsa_ctx* ctx, const void* ref_dev, int64_t ref_len, const void* fusions_dev, int32_t n_fusions, const void* reads_dev,
+                      int64_t reads_len, const void* pairs_dev, int64_t n_pairs)
+{
+    if (!ctx) return DSA_E_ARG;
+    const UploadArrays a{static_cast<const uint8_t*>(ref_dev), ref_len, static_cast<const dsa_fusion*>(fusions_dev), n_fusions,
+                         static_cast<const uint8_t*>(reads_dev), reads_len, static_cast<const dsa_pair*>(pairs_dev), n_pairs};
+    UploadShape shape;
+    if (int rc = upload_validate_device(ctx, ctx->main_stream(), a, &shape)) return rc;
+    if (int rc = upload_commit(ctx, ctx->main_stream(), a, hipMemcpyDeviceToDevice, shape)) return rc;
+    if (int rc = enqueue_plan(ctx)) return rc;
+    HIPC(hipStreamSynchronize(ctx->main_stream()));    // the caller's buffers are free again when dsa_upload_device returns
     HIPC(hipGetLastError());
     return DSA_OK;
 }

@@ -20,7 +20,7 @@ RECORD_DTYPE = np.dtype([(n, "<i4") for n in ("fusion_id", "frag", "read_end", "
 assert FUSION_DTYPE.itemsize == 20 and PAIR_DTYPE.itemsize == 20 and RECORD_DTYPE.itemsize == 40
 
 EXPORTS = ["dsa_create", "dsa_destroy", "dsa_get_limits", "dsa_tile_cols_for", "dsa_tile_cols_in_use", "dsa_last_error", "dsa_version", "dsa_build_flags", "dsa_device_count", "dsa_pick_device", "dsa_pick_device_among", "dsa_set_plan_options", "dsa_set_scratch_budget", "dsa_share_scratch", "dsa_align_batch",
-           "dsa_upload", "dsa_plan", "dsa_run", "dsa_download", "dsa_copy_records_device", "dsa_get_timing", "dsa_get_kernel_counts", "dsa_set_stream", "dsa_synchronize",
+           "dsa_upload", "dsa_upload_device", "dsa_plan", "dsa_run", "dsa_download", "dsa_copy_records_device", "dsa_get_timing", "dsa_get_kernel_counts", "dsa_set_stream", "dsa_synchronize",
            "dsa_stream_create", "dsa_stream_destroy", "dsa_stream_submit", "dsa_stream_collect", "dsa_stream_recollect", "dsa_stream_last_error",
            "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister"]
 
@@ -78,6 +78,7 @@ def load_library():
         batch = [vp, vp, i64, vp, i32, vp, i64, vp, i64]
         lib.dsa_align_batch.argtypes = batch + [vp, i64, ctypes.POINTER(i64)]
         lib.dsa_upload.argtypes = batch
+        lib.dsa_upload_device.argtypes = batch
         lib.dsa_plan.argtypes = [vp]
         lib.dsa_run.argtypes = [vp, ctypes.POINTER(i64)]
         lib.dsa_download.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
@@ -179,6 +180,15 @@ class Context:
         ref_bytes, fusions, read_bytes, pairs = _check_arrays(ref_bytes, fusions, read_bytes, pairs)
         rc = self.lib.dsa_upload(self.h, ref_bytes.ctypes.data, ref_bytes.size, fusions.ctypes.data, len(fusions),
                                  read_bytes.ctypes.data, read_bytes.size, pairs.ctypes.data, len(pairs))
+        if rc != 0:
+            self._err(rc)
+
+    def upload_device(self, view):
+        """dsa_upload_device: the batch is in memory of this context's device already.  `view` has the fields of bat_view
+        (defuse_amd.bat.View: four device pointers as integers and their counts); the arrays are copied device to device and
+        are free again on return."""
+        rc = self.lib.dsa_upload_device(self.h, view.ref_bytes, view.ref_bytes_len, view.fusions, view.n_fusions,
+                                        view.read_bytes, view.read_bytes_len, view.pairs, view.n_pairs)
         if rc != 0:
             self._err(rc)
 

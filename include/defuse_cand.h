@@ -105,6 +105,8 @@ void cand_session_destroy(cand_session* session);
 int cand_enumerate(cand_session* session, const cand_alignment* alignments, int64_t n, int32_t order,
                    cand_record* out, int64_t cap, int64_t* n_out, cand_timing* timing);
 
+/* The device-pointer twins of cand_enumerate, which leave the records in the session's device buffer for the batch
+ * assembly, are declared next to their consumer in defuse_bat.h. */
 const char* cand_last_error(void);
 
 #ifdef __cplusplus

@@ -172,6 +172,21 @@ int dsa_upload(dsa_ctx* ctx,
                const dsa_fusion* fusions, int32_t n_fusions,
                const uint8_t* read_bytes, int64_t read_bytes_len,
                const dsa_pair* pairs, int64_t n_pairs);
+/* The device-pointer twin of dsa_upload: the four arrays are in memory of the ctx's device already (an assembled batch,
+ * defuse_bat.h: bat_batch_view gives exactly these arguments).  They are complete when the call is made; the call copies
+ * them device to device into the ctx's own buffers, so they are free on return, and runs the same planning.  After it
+ * dsa_plan / dsa_run / dsa_download / dsa_copy_records_device behave exactly as after dsa_upload of the same arrays: the
+ * same checks with the same codes and the same lowest offending index (one small validation kernel and one small copy back
+ * instead of the host loops), the same tile width, plan and dsa_kernel_counts.
+ * The 32-bit path builds its work list from host arrays and stays with dsa_upload: a read beyond the 16-bit kernels' 7600
+ * bases or a window beyond their 16320 is DSA_E_LIMIT here.  A streamed device entry does not exist.
+ * A refused call, of this entry as of dsa_upload, copies nothing: the upload that was resident stays resident and can be
+ * planned and run again — unless it had pairs of the 32-bit path, whose host work list every upload call drops first. */
+int dsa_upload_device(dsa_ctx* ctx,
+                      const void* ref_dev, int64_t ref_len,
+                      const void* fusions_dev, int32_t n_fusions,
+                      const void* reads_dev, int64_t reads_len,
+                      const void* pairs_dev, int64_t n_pairs);
 /* Plans the sweep of the resident upload once more — everything dsa_upload does per candidate after its copies (sweep
  * order of the fusions and of the pairs inside a fusion, per-pair score bounds).  A caller that times the path per
  * batch calls dsa_plan + dsa_run per step, so that all work the reference does per candidate inside the loop of
