@@ -98,6 +98,22 @@ __host__ __device__ constexpr uint32_t drift2(int i) { return (uint32_t)(2 * i) 
 typedef unsigned short v2u __attribute__((ext_vector_type(2)));
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
 
+// The pruning threshold of the table sweeps, both fields at once.  A cell of row j is alive if a field is >= 4j - slack (biased);
+// the sweeps test x >= thr as max(x, thr - 1) != thr - 1 against
+//     tm2(j) = max(4j - slack + BIAS16 - 1, 0) in both fields,    0xFFFF in both past the lane's read.
+// The lane's part of it is the same in every row and every tile: thr_base(slack) holds BIAS16 - 1 - slack + THR_OFFSET in both
+// fields, a row adds the wave-uniform 4j to both with one v_add_u32 (no carry: the fields stay in [2207, 47819] for reads of at
+// most 7600 bases, slack in [0, 2 * 7600], rows up to three past the longest read), and the saturating packed subtraction of
+// THR_OFFSET is the clamp at 0.
+constexpr int THR_OFFSET = 16384;
+__device__ __forceinline__ uint32_t thr_base(int slack) { return (uint32_t)((int)BIAS16 - 1 - slack + THR_OFFSET) * 0x00010001u; }
+__device__ __forceinline__ uint32_t thr_of_row(uint32_t base, int j, bool in_read)
+{
+    const uint32_t e = base + (uint32_t)j * FOUR2;
+    const uint32_t t = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2u, e), (v2u){(unsigned short)THR_OFFSET, (unsigned short)THR_OFFSET}));
+    return in_read ? t : 0xFFFFFFFFu;
+}
+
 // packed maxima on biased fields, via fp16 maximum (v_pk_maximum3_f16 on gfx950)
 __device__ __forceinline__ uint32_t max2(uint32_t a, uint32_t b)
 {
@@ -119,6 +135,13 @@ __device__ __forceinline__ uint32_t min3u(uint32_t x)   // per field min(x, 3)
     const v2u three = {3, 3};
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(v2u, x), three));
 }
+
+// A value that is the same in every lane of the wave BY CONSTRUCTION (the result of a cross-lane reduction, a word all lanes read
+// from the same LDS or global address, anything derived from such values): said to the compiler, which otherwise sees a lane
+// value, keeps it in a VGPR and compiles every loop bound and branch on it as divergent control flow (v_cmp, exec masks) where
+// a scalar compare and a scalar branch do.  Only where all lanes that hold the value are active: inside a
+// lane-masked region it would hand every lane the FIRST ACTIVE lane's value.
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // lower bound of the pair's final score found at upload (k_rank_in_fusion), 0 = none
 __device__ __forceinline__ int pair_bound(const dsa_pair& pr) { return (int)pr.pad_[0] | ((int)pr.pad_[1] << 8); }
@@ -178,11 +201,12 @@ __device__ __forceinline__ WgView wg_groups(WgGroupsLds* gl, int f, int f_prev_o
     my_group = base + __builtin_popcountll(m & ((2ull << lane) - 1ull)) - 1;
     if (start && my_group < GSPLIT2) gl->group_f[my_group] = f;
     __syncthreads();
+    total = uniform(total);                  // every thread summed the same four LDS words
     WgView v;
     v.n_groups = total <= GSPLIT2 ? total : 0;
     v.list = gl->group_f;
 #pragma unroll
-    for (int k = 0; k < GMAX; ++k) v.f4[k] = k < total ? gl->group_f[k] : 0;
+    for (int k = 0; k < GMAX; ++k) v.f4[k] = k < total ? uniform(gl->group_f[k]) : 0;
     return v;
 }
 
@@ -267,6 +291,15 @@ __host__ __device__ __forceinline__ int64_t rowidx(int j, int lane) { return ((i
 constexpr uint32_t CODE_MASK = 0xFF00FF00u;   // rowcodes: byte codes; bytes 0 and 2 carry the table row / the two classes
 // unbiased V of one field
 __device__ __forceinline__ int half_of(uint32_t v, int h) { return (int)((v >> (16 * h)) & 0xFFFFu) - (int)BIAS16; }
+
+// One row group (four rows of a lane) of a plane as ONE 16-byte load.  `cond ? plane[k] : constant` on a uint4 reaches the
+// back end as four dword loads under four branches; a native vector load under one branch stays whole.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 load_group(const uint4* p)
+{
+    const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
 
 // ---------------------------------------------------------------------------------------------
 // K0: byte -> packed code, code16 = byte<<8.
@@ -1010,7 +1043,7 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
     uint64_t* __restrict__ masks = fb.masks;
     bool any = false;
     for (int k = 0; k < wgi.n_groups; ++k) any |= fl->tile[k] >= 0;
-    if (!any) return;                                   // uniform
+    if (!uniform(any)) return;                          // every thread read the same LDS words
     // tables for the agreed tile pair of every fusion of the workgroup
     build_tables<SPLIT, WT>(T, wgi.n_groups, [&](int gi, int i, uint32_t& q0, uint32_t& q1) {
         const int key = fl->tile[gi];
@@ -1056,7 +1089,8 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
     int Rw = R;                                          // wave maximum
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) Rw = max(Rw, __shfl_xor(Rw, d, 64));
-    if (Rw == 0) return;                                  // wave-uniform; no barriers below
+    Rw = uniform(Rw);
+    if (Rw == 0) return;                                  // no barriers below
     const bool has0 = has && li.c0 != NO_CHUNK, has1 = has && li.c1 != NO_CHUNK;
     const int c0 = has0 ? li.c0 : 0, c1 = has1 ? li.c1 : 0;
     const uint32_t* tb = T + (li.key_group >> 8) * (SPLIT ? TGROUP_SPLIT : TGROUP);
@@ -1079,8 +1113,9 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
     uint32_t bprev = BIAS2;
     const int ngq = (Rw >> 2) + 1;
     auto boundary = [&](int gq) -> uint4 {
-        const uint4 x0 = gq < stop0 ? bi0[(int64_t)gq * WAVE] : bias4;
-        const uint4 x1 = gq < stop1 ? bi1[(int64_t)gq * WAVE] : bias4;
+        uint4 x0 = bias4, x1 = bias4;                      // the stops are the lane's own: one 16-byte load per side under its mask
+        if (gq < stop0) x0 = load_group(bi0 + (int64_t)gq * WAVE);
+        if (gq < stop1) x1 = load_group(bi1 + (int64_t)gq * WAVE);
         return make_uint4((x0.x & 0xFFFFu) | (x1.x & 0xFFFF0000u), (x0.y & 0xFFFFu) | (x1.y & 0xFFFF0000u),
                           (x0.z & 0xFFFFu) | (x1.z & 0xFFFF0000u), (x0.w & 0xFFFFu) | (x1.w & 0xFFFF0000u));
     };
@@ -1259,7 +1294,7 @@ __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax
         // kernel's wave cycles at 2x150 (profiles/r04/mix_stats.txt).
         int stop_hi[NC];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) stop_hi[c] = NC + c < nch_wave ? load_tstop(tstop + (int64_t)w * g.nch + NC + c) : 0;
+        for (int c = 0; c < NC; ++c) stop_hi[c] = NC + c < nch_wave ? uniform(load_tstop(tstop + (int64_t)w * g.nch + NC + c)) : 0;
         for (int gq = 0; gq < ngq; ++gq) {
             uint4 v[NC], u[NC];
 #pragma unroll
@@ -1289,7 +1324,7 @@ __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax
     for (int gq = 0; gq < ngq; ++gq) {
         uint4 m = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
         for (int c = 0; c < nch_wave; ++c) {
-            const uint4 v = gq < load_tstop(tstop + (int64_t)w * g.nch + c) ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
+            const uint4 v = gq < uniform(load_tstop(tstop + (int64_t)w * g.nch + c)) ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
             m.x = max2(m.x, v.x);
             m.y = max2(m.y, v.y);
             m.z = max2(m.z, v.z);
@@ -1299,7 +1334,7 @@ __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax
         if (nch_wave <= TMASK_TILES) {
             uint4 t = make_uint4(0, 0, 0, 0);
             for (int c = 0; c < nch_wave; ++c) {
-                const uint4 v = gq < load_tstop(tstop + (int64_t)w * g.nch + c) ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
+                const uint4 v = gq < uniform(load_tstop(tstop + (int64_t)w * g.nch + c)) ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
                 t.x |= eq_bits(v.x, m.x, c);
                 t.y |= eq_bits(v.y, m.y, c);
                 t.z |= eq_bits(v.z, m.z, c);
@@ -1335,7 +1370,7 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
         auto wave_max = [](int v) {
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-            return v;
+            return uniform(v);
         };
         WaveInfo wi;                             // rows and tiles of the wave, from its own pairs
         wi.lq_max = wave_max(in_batch ? (int)pairs[p].read_len : 0);
@@ -1392,7 +1427,7 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
 template <int NW, bool SPLIT, bool LAST>
 __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, const uint32_t* __restrict__ rows1, const uint4* __restrict__ bi4,
                                                uint4* __restrict__ cm4, uint4* __restrict__ bo4, bool first_tile, int lq_max, int lq_lane,
-                                               int slack, int l_in, int stop_prev, int& last_bnd, const Geom& g, int tile)
+                                               uint32_t thr0, int l_in, int stop_prev, int& last_bnd, const Geom& g, int tile)
 {
     static_assert(NW % 4 == 0 && NW / 4 > FILL_PF && NW <= W, "table reads in flight");
     (void)g; (void)tile;
@@ -1412,7 +1447,8 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
         const uint4 b = b_n;
         const int gn = gq + 1 < ngq ? gq + 1 : gq;          // prefetch the next four rows' operands
         rc_n = rows1[(int64_t)gn * WAVE];
-        b_n = gn < stop_prev ? bi4[(int64_t)gn * WAVE] : bias4;   // past the left tile's stop: dead, V = 0
+        b_n = bias4;                                        // past the left tile's stop: dead, V = 0
+        if (gn < stop_prev) b_n = load_group(bi4 + (int64_t)gn * WAVE);   // uniform
         const uint32_t bv[4] = {b.x, b.y, b.z, b.w};
         uint32_t cmv[4] = {BIAS2, BIAS2, BIAS2, BIAS2}, bov[4] = {BIAS2, BIAS2, BIAS2, BIAS2};
         uint32_t alive_bits = 0;
@@ -1487,9 +1523,8 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
                     cmv[sidx] = max2(acc0, acc1);
                 }
                 // alive: a field >= thr = 4j - slack (biased).  Both fields at once: x >= thr <=> max(x, thr-1) != thr-1;
-                // rows past the lane's read compare against 0xFFFF, which nothing exceeds.
-                const int t1 = max(4 * j - slack + (int)BIAS16 - 1, 0);
-                const uint32_t tm2 = j <= lq_lane ? (uint32_t)t1 * 0x00010001u : 0xFFFFFFFFu;
+                // rows past the lane's read compare against 0xFFFF, which nothing exceeds (thr_of_row).
+                const uint32_t tm2 = thr_of_row(thr0, j, j <= lq_lane);
                 alive_bits |= pk_max_u16(cmv[sidx], tm2) ^ tm2;
                 if (!LAST) {
                     bov[sidx] = X[NW - 1] - drift2(NW - 1);
@@ -1513,14 +1548,16 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
                 uint4 bb = b_n;                                     // group gq + 1, already on its way
                 uint32_t in_prev = bv[3];                           // the boundary value of the row above the group: it enters by the diagonal
                 for (; g2 < ngq; ++g2) {
-                    if (g2 > gq + 1) bb = g2 < stop_prev ? bi4[(int64_t)g2 * WAVE] : bias4;
+                    if (g2 > gq + 1) {
+                        bb = bias4;
+                        if (g2 < stop_prev) bb = load_group(bi4 + (int64_t)g2 * WAVE);   // uniform
+                    }
                     const uint32_t bbv[5] = {in_prev, bb.x, bb.y, bb.z, bb.w};
                     uint32_t in_bits = 0;
 #pragma unroll
                     for (int sidx = 0; sidx < 5; ++sidx) {
                         const int j = 4 * g2 + sidx - 1;
-                        const int t1 = max(4 * j - slack + (int)BIAS16 - 1, 0);
-                        const uint32_t tm2 = j <= lq_lane ? (uint32_t)t1 * 0x00010001u : 0xFFFFFFFFu;
+                        const uint32_t tm2 = thr_of_row(thr0, j, j <= lq_lane);
                         in_bits |= pk_max_u16(bbv[sidx], tm2) ^ tm2;
                     }
                     if (__builtin_amdgcn_ballot_w64(in_bits != 0u) != 0) { resume = true; break; }
@@ -1618,7 +1655,7 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
     auto wave_max = [](int v) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-        return v;
+        return uniform(v);
     };
     WaveInfo wi;
     wi.lq_max = wave_max(lq_lane);
@@ -1633,7 +1670,7 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
     if (lane == 0 && live) atomicMax(&s_nch, wi.nch_max);
     if (__builtin_amdgcn_ballot_w64(exotic) != 0 && lane == 0) atomicOr(&s_exotic, 1);
     __syncthreads();
-    if (s_exotic != 0) {                         // uniform
+    if (uniform(s_exotic) != 0) {
         if (threadIdx.x == 0) {
             wg_tier[blockIdx.x] = TIER_GENERIC;
             atomicOr(&fb.ctr->need_tiers, 1u << TIER_GENERIC);
@@ -1641,10 +1678,11 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
         return;
     }
     if (threadIdx.x == 0) atomicAdd(&fb.ctr->fill_wgs[FILL_WGS_FAST + 2 * TIER + (WIDE ? 1 : 0)], 1u);   // this kernel sweeps the workgroup
-    const int nch_wg = s_nch;
+    const int nch_wg = uniform(s_nch);
 
     const uint32_t* tb = T + my_group * (SPLIT ? TGROUP_SPLIT : TGROUP);
     const uint32_t* rows1 = row_bytes + (int64_t)w * (g.lq1 >> 2) * WAVE + lane;
+    const uint32_t thr0 = thr_base(slack);
     int stop_prev = 0;                   // stored row groups of the tile to the left
     TileStops stops = {};
 
@@ -1669,9 +1707,9 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
         const uint4* bi4 = reinterpret_cast<const uint4*>(bnd + ((int64_t)w * g.nch + (c - 1)) * g.lq1 * WAVE) + lane;
         int last_bnd = 0, gq;
         if (c + 1 < wi.nch_max)
-            gq = sweep_tile_fast<WT, SPLIT, false>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g, c);
+            gq = sweep_tile_fast<WT, SPLIT, false>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, thr0, l_in, stop_prev, last_bnd, g, c);
         else
-            gq = sweep_tile_fast<WT, SPLIT, true>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, slack, l_in, stop_prev, last_bnd, g, c);
+            gq = sweep_tile_fast<WT, SPLIT, true>(tb, rows1, bi4, cm4, bo4, c == 0, wi.lq_max, lq_lane, thr0, l_in, stop_prev, last_bnd, g, c);
         if (lane == 0) DSA_STAT_ADD(g, DS_TILE_CYCLES + (c < DS_TILE_SLOTS ? c : DS_TILE_SLOTS - 1), clk.lap());
         // the dead remainder of the tile is not stored: its readers substitute V = 0 past the stop
         if (lane == 0) fb.tstop[(int64_t)w * g.nch + c] = gq;
@@ -1864,6 +1902,7 @@ __global__ __launch_bounds__(REPLAY_BLOCK, 5) void k_replay(FinishBufs fb, const
         int Rw = R;                                        // the wave steps as long as its longest task
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) Rw = max(Rw, __shfl_xor(Rw, d, 64));
+        Rw = uniform(Rw);
         // lane q is at row t - q in step t; operands are fetched two steps ahead
         uint32_t rc_n = row_code(1 - q), rc_nn = row_code(2 - q);
         uint32_t b_n = q == 0 ? boundary(1) : BIAS2, b_nn = q == 0 ? boundary(2) : BIAS2;

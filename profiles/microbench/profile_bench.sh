@@ -13,12 +13,13 @@ O=$R/gpurun_out/profile_bench${PB_SUFFIX}
 mkdir -p $O
 export PB_SUFFIX PB_WORKLOAD
 B="python3 $R/bench.py --profile-run --warmup 1 $PB_ARGS"
-rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- $B --steps 20 > $O/kt.log 2>&1 || exit 1
+# the counter passes are runs of their own, without tracing; every pass under its own time limit, and nothing after one that fails
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- $B --steps 20 > $O/kt.log 2>&1 || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$c -o p --output-format csv -- $B --steps 3 > $O/pmc_$c.log 2>&1 || exit 1
+  timeout -k 10 240 rocprofv3 --pmc $c -d $O/pmc_$c -o p --output-format csv -- $B --steps 3 > $O/pmc_$c.log 2>&1 || exit 1
 done
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU -d $O/pmc1 -o p1 --output-format csv -- $B --steps 3 > $O/pmc1.log 2>&1 || exit 1
-rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_WAVES -d $O/pmc2 -o p2 --output-format csv -- $B --steps 3 > $O/pmc2.log 2>&1 || exit 1
+timeout -k 10 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU -d $O/pmc1 -o p1 --output-format csv -- $B --steps 3 > $O/pmc1.log 2>&1 || exit 1
+timeout -k 10 240 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_WAVES -d $O/pmc2 -o p2 --output-format csv -- $B --steps 3 > $O/pmc2.log 2>&1 || exit 1
 python3 - <<'PY'
 import collections, csv, glob, json, os, shutil, sys
 R = os.environ["GRAFT_REPO_ROOT"]
