@@ -18,12 +18,7 @@
 //   (4) pairs, fusions and one 16-byte segment descriptor per read and per window are written;
 //   (5) the gather (k_bat_gather) copies the segments, reads reversed and complemented where revcomp is set.
 //
-// The gather.  A group of G lanes owns a segment; lane i forms the aligned OUTPUT dword i (+ G, + 2G ...) of the segment from
-// two aligned source dwords (v_alignbyte_b32), reversed with a byte permute (v_perm_b32) and complemented in registers, so a
-// group stores G consecutive dwords per step.  read_bytes is a plain concatenation: the dword in which a segment begins or
-// ends also holds its neighbours' bytes, and a read of 1, 2, 3 or 5 bytes may own no whole dword at all.  A dword store
-// therefore goes only to dwords that lie wholly inside the segment; the up to three bytes before the first and after the last
-// of them go out as byte stores of the same group.  No byte is written by two groups, none by a read-modify-write.
+// The gather kernel, its segment record and the window store's struct are in bat_shared.hpp (pred_api.hip uses them too).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -33,6 +28,7 @@
 #include <vector>
 
 #include "../../include/defuse_bat.h"
+#include "bat_shared.hpp"
 #include "hip_host.hpp"
 
 namespace {
@@ -40,6 +36,9 @@ namespace {
 using hiphost::DeviceBuffer;
 using hiphost::GrowSize;
 using hiphost::grid_of;
+using batdev::Seg;
+using batdev::SRC_PAD;
+using batdev::WindowsView;
 using u64 = unsigned long long;
 
 thread_local std::string g_bat_err;
@@ -47,11 +46,10 @@ thread_local std::string g_bat_err;
 #define BAT_HIP(call) HIPHOST_TRY(g_bat_err, call)
 #define BAT_FAIL(code, ...) hiphost::fail(g_bat_err, code, __VA_ARGS__)
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = batdev::GATHER_BLOCK;
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int READ_GROUP = 16;        // lanes per read: 150 bases are 38 dwords, three steps of 16
 constexpr int WINDOW_GROUP = 64;      // lanes per window: a few hundred bases and more
-constexpr size_t SRC_PAD = 8;         // the gather loads the aligned dword after the one a segment ends in
 
 __host__ __device__ inline uint32_t read_key(int32_t fragment, int32_t read_end)
 {
@@ -106,12 +104,6 @@ struct ReadsView {
     int64_t n_unique;
 };
 
-struct WindowsView {
-    const uint32_t* wkey;       // n fusion ids, ascending as unsigned, distinct
-    const dsa_fusion* wfus;     // in the same order: offsets into the windows' ref bytes
-    int64_t n;
-};
-
 // ---- assembly ---------------------------------------------------------------------------------------------------------
 
 struct Totals {
@@ -119,13 +111,6 @@ struct Totals {
     u64 ref_total;              // bytes of ref_bytes
     uint32_t bad;               // lowest record whose fusion_id has no windows, NONE if there is none
     uint32_t n_used;            // fusions of the batch
-};
-
-// one copied or reverse-complemented run of bytes of a gather
-struct Seg {
-    int64_t src;                // offset into the source bytes
-    int32_t dst;                // offset into the output (totals are below 2^31)
-    uint32_t len_rev;           // length in bits 0-30, reverse complement in bit 31
 };
 
 __global__ void k_bat_lookup(const cand_record* __restrict__ cand, int64_t n, ReadsView r, WindowsView w, u64* __restrict__ rlen,
@@ -219,64 +204,6 @@ __global__ void k_bat_pairs(const cand_record* __restrict__ cand, int64_t n, Rea
     seg[k] = Seg{have ? r.uoff[ridx[k]] : 0, p.read_off, (have ? len : 0u) | (c.revcomp ? 0x80000000u : 0u)};
 }
 
-// tools/Common.cpp:32-54: A<->T, C<->G in either case, every other byte value as it is.  Clearing bit 5 folds the case and
-// maps no other byte onto a letter; A ^ T = 0x15, C ^ G = 0x04.
-__device__ inline uint32_t complement_byte(uint32_t b)
-{
-    const uint32_t u = b & 0xDFu;
-    const uint32_t m = (u == 0x41u || u == 0x54u) ? 0x15u : (u == 0x43u || u == 0x47u) ? 0x04u : 0u;
-    return b ^ m;
-}
-
-__device__ inline uint32_t complement_word(uint32_t v)
-{
-    return complement_byte(v & 0xFFu) | (complement_byte((v >> 8) & 0xFFu) << 8) | (complement_byte((v >> 16) & 0xFFu) << 16) |
-           (complement_byte(v >> 24) << 24);
-}
-
-// the four bytes at byte offset a of the source, from the two aligned dwords around them (the source is padded by SRC_PAD)
-__device__ inline uint32_t load_word(const uint32_t* __restrict__ src, int64_t a)
-{
-    const uint32_t lo = src[a >> 2], hi = src[(a >> 2) + 1];
-    return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)a & 3u);
-}
-
-template <int G>
-__global__ __launch_bounds__(BLOCK) void k_bat_gather(const Seg* __restrict__ seg, int64_t n_seg, const uint8_t* __restrict__ src, int64_t src_len,
-                                                       uint8_t* __restrict__ dst, int64_t dst_len)
-{
-    const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const int64_t k = t / G;
-    const int lane = (int)(t % G);
-    if (k >= n_seg) return;
-    const Seg s = seg[k];
-    const int64_t len = (int64_t)(s.len_rev & 0x7FFFFFFFu);
-    const bool rev = (s.len_rev >> 31) != 0;
-    const int64_t d0 = s.dst, d1 = d0 + len;
-    if (len == 0 || d0 < 0 || d1 > dst_len || s.src < 0 || s.src + len > src_len) return;
-    const uint32_t* __restrict__ srcw = reinterpret_cast<const uint32_t*>(src);
-    uint32_t* __restrict__ dstw = reinterpret_cast<uint32_t*>(dst);
-    // the dwords of the output that lie wholly inside [d0, d1): [w0, w1), none if w1 <= w0
-    const int64_t w0 = (d0 + 3) & ~(int64_t)3, w1 = d1 & ~(int64_t)3;
-    for (int64_t p = w0 + 4 * lane; p < w1; p += 4 * G) {
-        const int64_t i = p - d0;                            // bytes i .. i + 3 of the oriented read
-        uint32_t v;
-        if (!rev) v = load_word(srcw, s.src + i);
-        else v = complement_word(__builtin_bswap32(load_word(srcw, s.src + len - 4 - i)));      // (bswap is one v_perm_b32)
-        dstw[p >> 2] = v;
-    }
-    // head [d0, h1) and tail [t0, d1): at most three bytes each, one lane per byte, from the far end of the group
-    const int64_t h1 = w0 < d1 ? w0 : d1;
-    const int64_t t0 = w1 > h1 ? w1 : h1;
-    const int64_t nh = h1 - d0, nt = d1 - t0;
-    const int64_t b = G - 1 - lane;
-    if (b < nh + nt) {
-        const int64_t p = b < nh ? d0 + b : t0 + (b - nh);
-        const int64_t i = p - d0;
-        dst[p] = rev ? (uint8_t)complement_byte(src[s.src + len - 1 - i]) : src[s.src + i];
-    }
-}
-
 int bits_for(int64_t n)      // bits that hold 0 .. n - 1, at least one
 {
     int b = 1;
@@ -295,16 +222,6 @@ struct bat_reads {
     DeviceBuffer<int64_t> uoff;
     DeviceBuffer<int32_t> ulen;
     ReadsView view() const { return ReadsView{ukey.p, uoff.p, ulen.p, n_unique}; }
-};
-
-struct bat_windows {
-    int device = -1;
-    int64_t n = 0, bytes_len = 0;
-    hiphost::Stream st;
-    DeviceBuffer<uint8_t> bytes;
-    DeviceBuffer<uint32_t> wkey;
-    DeviceBuffer<dsa_fusion> wfus;
-    WindowsView view() const { return WindowsView{wkey.p, wfus.p, n}; }
 };
 
 struct bat_batch {

@@ -25,6 +25,7 @@
 #include "../../include/defuse_dsa.h"
 #include "../../include/defuse_eval.h"
 #include "hip_host.hpp"
+#include "pred_shared.hpp"
 
 namespace {
 
@@ -247,6 +248,7 @@ struct eval_ctx {
     hiphost::Stream st;
     hiphost::Event ev[5];
     eval_timing timing{};
+    int64_t resident_groups = -1;                                   // groups[0 .. resident_groups) are the latest successful call's; -1: none
     DeviceBuffer<int32_t, hiphost::GrowSize> rec;                   // the host entry's copy of the records (ten ints each)
     DeviceBuffer<int32_t, hiphost::GrowSize> rf, rs, qf, qs, score, rs_sorted;
     DeviceBuffer<uint32_t, hiphost::GrowSize> ghead, gid1, gstart, key1, key1_sorted, idx0, idx1, sidx, keep, koff;
@@ -297,13 +299,18 @@ int eval_run(eval_ctx* c, const void* records, bool on_device, int64_t n, eval_g
 {
     if (!c || n < 0 || (n && !records) || !n_groups || !n_kept || group_cap < 0 || kept_cap < 0) {
         g_eval_err = "eval_groups: null pointer or negative count";
+        if (c) c->resident_groups = -1;
         return DSA_E_ARG;
     }
+    c->resident_groups = -1;                                        // until this call has succeeded
     *n_groups = *n_kept = 0;
     // 32-bit scans, slots and sort counts
     if (n >= INT32_MAX - 1) { g_eval_err = "more than 2^31 - 2 records in one call"; return DSA_E_LIMIT; }
     c->timing = eval_timing{};
-    if (n == 0) return DSA_OK;
+    if (n == 0) {
+        c->resident_groups = 0;
+        return DSA_OK;
+    }
     EVAL_HIP(hipSetDevice(c->device));
     hipStream_t st = c->st;
     const int rc = eval_reserve(c, (size_t)n);
@@ -386,6 +393,7 @@ int eval_run(eval_ctx* c, const void* records, bool on_device, int64_t n, eval_g
     EVAL_HIP(hipEventRecord(c->ev[4], st));
     EVAL_HIP(hipStreamSynchronize(st));
     c->timing.download_ms = hiphost::elapsed(c->ev[3], c->ev[4]);
+    c->resident_groups = cnt.n_groups;
     return DSA_OK;
 }
 
@@ -432,6 +440,17 @@ int eval_groups_device(eval_ctx* c, const void* records_device, int64_t n, eval_
                        int64_t kept_cap, int64_t* n_kept)
 {
     return eval_run(c, records_device, true, n, groups, group_cap, n_groups, kept, kept_cap, n_kept);
+}
+
+// include/defuse_pred.h; here because it reads the ctx.  The groups are complete: eval_run has synchronised its stream.
+int pred_predict_resident(pred_ctx* ctx, const pred_tasks* tasks, const eval_ctx* eval)
+{
+    if (!ctx || !tasks || !eval) return predint::fail(DSA_E_ARG, "pred_predict_resident: no %s", !ctx ? "ctx" : !tasks ? "tasks" : "eval ctx");
+    if (eval->resident_groups < 0) {
+        predint::clear(ctx);
+        return predint::fail(DSA_E_ARG, "pred_predict_resident: the eval ctx has no completed evaluation (none yet, or its latest call failed or was refused)");
+    }
+    return predint::predict_device("pred_predict_resident", ctx, tasks, eval->groups.p, eval->resident_groups, eval->device);
 }
 
 int eval_get_timing(const eval_ctx* c, eval_timing* out)
