@@ -32,6 +32,7 @@
 namespace {
 
 using batdev::Seg64;
+using predint::DevTask;
 using batdev::SRC_PAD;
 using hiphost::DeviceBuffer;
 using hiphost::GrowSize;
@@ -49,17 +50,6 @@ constexpr int REM_GROUP = 16;         // lanes per remainder: none to a few hund
 constexpr int WINDOW_GROUP = 64;      // lanes per window part: a few hundred bases and more
 
 static_assert(sizeof(pred_task) == 56 && sizeof(pred_result) == 56 && sizeof(pred_device_view) == 40 && sizeof(pred_timing) == 40, "C ABI layout");
-
-// a task on the device: pred_task without its id (the ids are a column of their own), with its windows' offsets
-struct DevTask {
-    int64_t rem_off[2];
-    int32_t rem_len[2];
-    int32_t win_off[2];         // of window 0 / 1 in the byte pool of bat_windows
-    int32_t seq_start[2];
-    int32_t seq_len[2];
-    int32_t seq_strand[2];
-    int32_t pad_[2];
-};
 
 // the first index in [0, n) with a[index] >= x
 __device__ inline int64_t lower_bound(const uint32_t* __restrict__ a, int64_t n, uint32_t x)
@@ -139,16 +129,6 @@ __global__ __launch_bounds__(BLOCK) void k_pred_segments(const eval_group* __res
 }
 
 }  // namespace
-
-struct __attribute__((visibility("hidden"))) pred_tasks {
-    int device = -1;
-    int64_t n = 0, rem_len = 0;
-    const bat_windows* windows = nullptr;
-    hiphost::Stream st;
-    DeviceBuffer<uint8_t> rem;             // rem_len + SRC_PAD
-    DeviceBuffer<uint32_t> tkey;           // n fusion ids, ascending as unsigned, distinct
-    DeviceBuffer<DevTask> task;            // in the same order
-};
 
 struct __attribute__((visibility("hidden"))) pred_ctx {
     int device = -1;
