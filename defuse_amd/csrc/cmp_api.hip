@@ -22,16 +22,25 @@
 
 #include "../../include/defuse_cmp.h"
 #include "../../include/defuse_dsa.h"
+#include "cmp_shared.hpp"
 #include "hip_host.hpp"
+
+namespace cmpshared {
+std::string& cmp_err()
+{
+    thread_local std::string e;
+    return e;
+}
+}  // namespace cmpshared
 
 namespace {
 
+using cmpshared::Side;
+using cmpshared::cmp_err;
 using hiphost::DeviceBuffer;
 using hiphost::grid_of;
 
-thread_local std::string g_cmp_err;
-
-#define CMP_HIP(call) HIPHOST_TRY(g_cmp_err, call)
+#define CMP_HIP(call) HIPHOST_TRY(cmp_err(), call)
 
 constexpr int BIN_LENGTH = 1 << 15;            // tools/clustermatepairs.cpp:385 (binLength)
 constexpr uint32_t REF_MASK = 0x0FFFFFFFu;
@@ -211,46 +220,23 @@ __global__ void k_cmp_same_keys(const unsigned long long* __restrict__ a, const 
     if (i < n && a[i] != b[i]) globals[2] = 1;
 }
 
-struct Side {
-    DeviceBuffer<unsigned long long> key, key_sorted, uniq;
-    DeviceBuffer<cmp_packed> pay, pay_sorted;
-    DeviceBuffer<uint32_t> idx, idx_sorted, off;
-    DeviceBuffer<int> run_len;
-    int64_t n = 0;
-};
-
 }  // namespace
-
-struct cmp_binner {
-    int device = -1;
-    hiphost::Stream st;
-    hiphost::Event ev[2];
-    int64_t n_records = 0, n_fragments = 0;
-    DeviceBuffer<cmp_record> recs;
-    DeviceBuffer<uint32_t> frag_start, cnt[4], off_first, off_second;
-    DeviceBuffer<unsigned long long> globals;
-    DeviceBuffer<uint8_t> tmp;
-    DeviceBuffer<int> n_runs;
-    Side side[2];
-    int64_t n_keys = 0;
-    bool ran = false;
-};
 
 extern "C" {
 
-const char* cmp_last_error(void) { return g_cmp_err.c_str(); }
+const char* cmp_last_error(void) { return cmp_err().c_str(); }
 
 int cmp_bin_create(cmp_binner** out, int device)
 {
     if (!out) return DSA_E_ARG;
     *out = nullptr;
-    if (hiphost::check_device(device, &g_cmp_err)) return DSA_E_DEVICE;
+    if (hiphost::check_device(device, &cmp_err())) return DSA_E_DEVICE;
     CMP_HIP(hipSetDevice(device));
     cmp_binner* b = new cmp_binner();
     b->device = device;
     if (b->st.create(hipStreamNonBlocking) != hipSuccess || b->ev[0].create() != hipSuccess || b->ev[1].create() != hipSuccess) {
         delete b;
-        g_cmp_err = "cannot create a stream";
+        cmp_err() = "cannot create a stream";
         return DSA_E_DEVICE;
     }
     *out = b;
@@ -268,7 +254,7 @@ void cmp_bin_destroy(cmp_binner* b)
 int cmp_bin_reserve(cmp_binner* b, int64_t n_records, int64_t n_fragments)
 {
     if (!b || n_records < 0 || n_fragments < 0) return DSA_E_ARG;
-    if (n_records >= ((int64_t)1 << 32) - 1) { g_cmp_err = "more than 2^32 alignment records in one call"; return DSA_E_LIMIT; }
+    if (n_records >= ((int64_t)1 << 32) - 1) { cmp_err() = "more than 2^32 alignment records in one call"; return DSA_E_LIMIT; }
     CMP_HIP(hipSetDevice(b->device));
     b->n_records = n_records;
     b->n_fragments = n_fragments;
@@ -343,7 +329,7 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
     }
     // (a 32-bit scan: the totals must fit; the counts of one fragment are far below that)
     if ((uint64_t)totals[0] >= ((uint64_t)1 << 31) || (uint64_t)totals[1] >= ((uint64_t)1 << 31)) {
-        g_cmp_err = "more than 2^31 bin-pair entries in one call";
+        cmp_err() = "more than 2^31 bin-pair entries in one call";
         return DSA_E_LIMIT;
     }
     for (int s = 0; s < 2; ++s) {
@@ -356,7 +342,7 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
         CMP_HIP(S.idx.reserve((size_t)S.n));
         CMP_HIP(S.idx_sorted.reserve((size_t)S.n));
         CMP_HIP(S.uniq.reserve((size_t)S.n));
-        CMP_HIP(S.run_len.reserve((size_t)S.n));
+        CMP_HIP(S.run_len.reserve((size_t)S.n + 1));          // the scan below reads run_len[runs], and runs can be S.n
         CMP_HIP(S.off.reserve((size_t)S.n + 1));
     }
     if (nf)
@@ -384,14 +370,14 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
         }));
     }
     // every bin pair has entries on both sides (each insert() pair of the reference feeds both lists)
-    if (runs[0] != runs[1]) { g_cmp_err = "internal: the two sides disagree on the bin pairs"; return DSA_E_DEVICE; }
+    if (runs[0] != runs[1]) { cmp_err() = "internal: the two sides disagree on the bin pairs"; return DSA_E_DEVICE; }
     if (runs[0])
         hipLaunchKernelGGL(k_cmp_same_keys, dim3(grid_of(runs[0])), dim3(256), 0, st, b->side[0].uniq.p, b->side[1].uniq.p, (int64_t)runs[0], b->globals.p);
     CMP_HIP(hipEventRecord(b->ev[1], st));
     CMP_HIP(hipMemcpyAsync(glob, b->globals.p, sizeof glob, hipMemcpyDeviceToHost, st));
     CMP_HIP(hipStreamSynchronize(st));
     CMP_HIP(hipGetLastError());
-    if (glob[2]) { g_cmp_err = "internal: the two sides disagree on the bin pairs"; return DSA_E_DEVICE; }
+    if (glob[2]) { cmp_err() = "internal: the two sides disagree on the bin pairs"; return DSA_E_DEVICE; }
     b->n_keys = runs[0];
     stats->n_keys = runs[0];
     stats->n_first = b->side[0].n;
@@ -403,7 +389,7 @@ int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
 
 int cmp_bin_fetch(cmp_binner* b, uint64_t* keys, int64_t* off_first, int64_t* off_second, cmp_packed* first, cmp_packed* second)
 {
-    if (!b || !b->ran) { g_cmp_err = "cmp_bin_fetch before a successful cmp_bin_run"; return DSA_E_ARG; }
+    if (!b || !b->ran) { cmp_err() = "cmp_bin_fetch before a successful cmp_bin_run"; return DSA_E_ARG; }
     if (!off_first || !off_second) return DSA_E_ARG;
     CMP_HIP(hipSetDevice(b->device));
     const int64_t nk = b->n_keys;
@@ -428,7 +414,7 @@ int cmp_bin_fetch(cmp_binner* b, uint64_t* keys, int64_t* off_first, int64_t* of
 
 int cmp_bin_fetch_part(cmp_binner* b, int which, int64_t from, int64_t n, cmp_packed* out)
 {
-    if (!b || !b->ran) { g_cmp_err = "cmp_bin_fetch_part before a successful cmp_bin_run"; return DSA_E_ARG; }
+    if (!b || !b->ran) { cmp_err() = "cmp_bin_fetch_part before a successful cmp_bin_run"; return DSA_E_ARG; }
     if (which < 0 || which > 1 || from < 0 || n < 0 || from + n > b->side[which].n || (n && !out)) return DSA_E_ARG;
     CMP_HIP(hipSetDevice(b->device));
     if (n) CMP_HIP(hipMemcpy(out, b->side[which].pay_sorted.p + from, (size_t)n * sizeof(cmp_packed), hipMemcpyDeviceToHost));

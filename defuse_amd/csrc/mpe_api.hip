@@ -1381,39 +1381,38 @@ __global__ __launch_bounds__(WV) __attribute__((amdgpu_waves_per_eu(MPE_WPE, MPE
 
 extern "C" const char* mpe_last_error(void) { return g_mpe_err.empty() ? g_mpe_err_sharded.c_str() : g_mpe_err.c_str(); }
 
-extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int64_t* prob_off, int32_t n_problems,
-                                 const double* x, const double* y, const double* u, const int32_t* to_xo,
-                                 const int32_t* to_yo, int32_t* n_clusters, uint16_t* member, int32_t* status,
-                                 mpe_timing* timing)
+namespace {
+
+// what both entries check before anything is allocated
+int check_batch(int device, const mpe_params* params, const int64_t* prob_off, int32_t n_problems)
 {
-    mpe_timing t{};
     if (!params || n_problems < 0 || (n_problems && !prob_off)) { g_mpe_err = "bad arguments"; return DSA_E_ARG; }
-    const int64_t n_mp = n_problems ? prob_off[n_problems] : 0;
-    t.n_problems = n_problems;
-    t.n_mate_pairs = n_mp;
-    if (n_problems == 0) { if (timing) *timing = t; return DSA_OK; }
+    if (n_problems == 0) return DSA_OK;
     if (hiphost::check_device(device, &g_mpe_err)) return DSA_E_DEVICE;
     MPE_HIP(hipSetDevice(device));
     for (int p = 0; p < n_problems; ++p) {
         const int64_t n = prob_off[p + 1] - prob_off[p];
         if (n < 0 || n > 0x7FFFFFF) { g_mpe_err = "problem too large"; return DSA_E_LIMIT; }
     }
+    return DSA_OK;
+}
+
+// The batch with its five arrays on the device (after check_batch, n_problems > 0, the device current); the member masks are
+// written to d_member on the device.  Both entries run this.
+int cluster_batch_on_device(const mpe_params* params, const int64_t* prob_off, int32_t n_problems, const double* d_x, const double* d_y,
+                            const double* d_u, const int32_t* d_txo, const int32_t* d_tyo, int32_t* n_clusters, uint16_t* d_member,
+                            int32_t* status, mpe_timing* timing)
+{
+    mpe_timing t{};
+    const int64_t n_mp = prob_off[n_problems];
+    t.n_problems = n_problems;
+    t.n_mate_pairs = n_mp;
     DeviceBuffer<int64_t> d_off;
-    DeviceBuffer<double> d_x, d_y, d_u;
-    DeviceBuffer<int32_t> d_txo, d_tyo, d_nc, d_status;
-    DeviceBuffer<uint16_t> d_member;
+    DeviceBuffer<int32_t> d_nc, d_status;
     DeviceBuffer<unsigned long long> d_iters;
     MPE_HIP(d_off.reserve(n_problems + 1));
-    MPE_HIP(d_x.reserve(n_mp)); MPE_HIP(d_y.reserve(n_mp)); MPE_HIP(d_u.reserve(n_mp)); MPE_HIP(d_txo.reserve(n_mp)); MPE_HIP(d_tyo.reserve(n_mp));
-    MPE_HIP(d_nc.reserve(n_problems)); MPE_HIP(d_status.reserve(n_problems)); MPE_HIP(d_member.reserve(n_mp)); MPE_HIP(d_iters.reserve(1));
+    MPE_HIP(d_nc.reserve(n_problems)); MPE_HIP(d_status.reserve(n_problems)); MPE_HIP(d_iters.reserve(1));
     MPE_HIP(hipMemcpy(d_off.p, prob_off, (n_problems + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (n_mp) {
-        MPE_HIP(hipMemcpy(d_x.p, x, n_mp * sizeof(double), hipMemcpyHostToDevice));
-        MPE_HIP(hipMemcpy(d_y.p, y, n_mp * sizeof(double), hipMemcpyHostToDevice));
-        MPE_HIP(hipMemcpy(d_u.p, u, n_mp * sizeof(double), hipMemcpyHostToDevice));
-        MPE_HIP(hipMemcpy(d_txo.p, to_xo, n_mp * sizeof(int32_t), hipMemcpyHostToDevice));
-        MPE_HIP(hipMemcpy(d_tyo.p, to_yo, n_mp * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
     MPE_HIP(hipMemset(d_iters.p, 0, sizeof(unsigned long long)));
     // DEFUSE_MPE_DUMP_ITERS=<file>: per problem twelve int64 — [0] the chosen K, [K] the EM iterations of the fit with K
     // components, [11] those of the refit — for the problems a wave fits (tests compare them with the restatement's)
@@ -1520,8 +1519,8 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
             MPE_HIP(d_km_off.reserve(km_off.size()));
             MPE_HIP(hipMemcpy(d_km_off.p, km_off.data(), km_off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
             MPE_HIP(d_km_scratch.reserve((size_t)(MPE_KMAX - 1) * (size_t)km_off.back() * KM_ROW_DOUBLES));
-            hipLaunchKernelGGL(k_mpe_seed, dim3((unsigned)n_large), dim3(WV), 0, s_wave, *params, d_off.p, p0, d_order.p, d_x.p, d_y.p, d_u.p, d_txo.p,
-                               d_tyo.p, d_wd.p, d_work.p, d_seeds.p);
+            hipLaunchKernelGGL(k_mpe_seed, dim3((unsigned)n_large), dim3(WV), 0, s_wave, *params, d_off.p, p0, d_order.p, d_x, d_y, d_u, d_txo,
+                               d_tyo, d_wd.p, d_work.p, d_seeds.p);
             // The k-means kernel ends in a long tail: its longest waves (64 start-ups of the largest problems in lockstep)
             // run for tens of milliseconds with most of the card idle.  So the problems go in shares on streams of their own
             // (k-means, then EM, each): the groups of the largest problems in the first, all smaller ones in the last, whose
@@ -1542,11 +1541,11 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
             auto share = [&](hipStream_t st, int g0, int g1) {         // groups [g0, g1) of the sorted problems
                 if (g0 >= g1) return;
                 const int r0 = g0 * WV, n = std::min(n_large, g1 * WV) - r0;
-                hipLaunchKernelGGL(k_mpe_kmeans, dim3((unsigned)((g1 - g0) * (MPE_KMAX - 1))), dim3(WV), 0, st, d_off.p, p0, n, g1 - g0, d_order.p + r0, d_x.p,
-                                   d_y.p, d_wi.p, d_iwork.p, d_seeds.p + r0, d_km_off.p + g0, (int64_t)km_off.back(), d_km_scratch.p,
+                hipLaunchKernelGGL(k_mpe_kmeans, dim3((unsigned)((g1 - g0) * (MPE_KMAX - 1))), dim3(WV), 0, st, d_off.p, p0, n, g1 - g0, d_order.p + r0, d_x,
+                                   d_y, d_wi.p, d_iwork.p, d_seeds.p + r0, d_km_off.p + g0, (int64_t)km_off.back(), d_km_scratch.p,
                                    d_km_ifault.p + (size_t)r0 * (MPE_KMAX + 1));
-                hipLaunchKernelGGL(k_mpe_problem_wave, dim3((unsigned)n), dim3(WV), 0, st, *params, d_off.p, p0, d_order.p + r0, d_x.p,
-                                   d_y.p, d_u.p, d_txo.p, d_tyo.p, d_wd.p, d_wi.p, d_work.p, d_iwork.p, d_nc.p, d_member.p, d_status.p,
+                hipLaunchKernelGGL(k_mpe_problem_wave, dim3((unsigned)n), dim3(WV), 0, st, *params, d_off.p, p0, d_order.p + r0, d_x,
+                                   d_y, d_u, d_txo, d_tyo, d_wd.p, d_wi.p, d_work.p, d_iwork.p, d_nc.p, d_member, d_status.p,
                                    d_iters.p, d_by_k.p, d_ll_by_k.p, d_seeds.p + r0, d_km_ifault.p + (size_t)r0 * (MPE_KMAX + 1));
             };
             const int n_shares = (int)cuts.size() - 1;                 // the last share on s_wave itself, the others on streams of their own
@@ -1564,11 +1563,11 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
         if (n_small) {
             const int64_t n_fit = (int64_t)n_small * MPE_KMAX;
             hipLaunchKernelGGL(k_mpe_fit, dim3((unsigned)((n_fit + 63) / 64)), dim3(64), 0, 0, *params, d_off.p, p0, n_large, n_small,
-                               d_order.p, d_x.p, d_y.p, d_u.p, d_txo.p, d_tyo.p, d_wd.p, d_wi.p, d_work.p, d_iwork.p, d_bic.p, d_state.p,
+                               d_order.p, d_x, d_y, d_u, d_txo, d_tyo, d_wd.p, d_wi.p, d_work.p, d_iwork.p, d_bic.p, d_state.p,
                                d_iters.p);
             hipLaunchKernelGGL(k_mpe_final, dim3((unsigned)((n_small + 63) / 64)), dim3(64), 0, 0, *params, d_off.p, p0, n_large, n_small,
-                               d_order.p, d_x.p, d_y.p, d_u.p, d_txo.p, d_tyo.p, d_wd.p, d_wi.p, d_work.p, d_iwork.p, d_bic.p, d_state.p,
-                               d_nc.p, d_member.p, d_status.p, d_iters.p);
+                               d_order.p, d_x, d_y, d_u, d_txo, d_tyo, d_wd.p, d_wi.p, d_work.p, d_iwork.p, d_bic.p, d_state.p,
+                               d_nc.p, d_member, d_status.p, d_iters.p);
         }
         MPE_HIP(hipEventRecord(e2, s_wave));
         MPE_HIP(hipStreamWaitEvent(0, e2, 0));
@@ -1580,7 +1579,6 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
     }
     MPE_HIP(hipMemcpy(n_clusters, d_nc.p, n_problems * sizeof(int32_t), hipMemcpyDeviceToHost));
     MPE_HIP(hipMemcpy(status, d_status.p, n_problems * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (n_mp) MPE_HIP(hipMemcpy(member, d_member.p, n_mp * sizeof(uint16_t), hipMemcpyDeviceToHost));
     unsigned long long it = 0;
     MPE_HIP(hipMemcpy(&it, d_iters.p, sizeof it, hipMemcpyDeviceToHost));
 
@@ -1625,6 +1623,47 @@ extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int
     for (int p = 0; p < n_problems; ++p) t.n_failed += status[p] != 0;
     if (timing) *timing = t;
     return DSA_OK;
+}
+
+}  // namespace
+
+extern "C" int mpe_cluster_batch(int device, const mpe_params* params, const int64_t* prob_off, int32_t n_problems,
+                                 const double* x, const double* y, const double* u, const int32_t* to_xo,
+                                 const int32_t* to_yo, int32_t* n_clusters, uint16_t* member, int32_t* status,
+                                 mpe_timing* timing)
+{
+    if (const int rc = check_batch(device, params, prob_off, n_problems)) return rc;
+    if (n_problems == 0) { if (timing) *timing = mpe_timing{}; return DSA_OK; }
+    const int64_t n_mp = prob_off[n_problems];
+    DeviceBuffer<double> d_x, d_y, d_u;
+    DeviceBuffer<int32_t> d_txo, d_tyo;
+    DeviceBuffer<uint16_t> d_member;
+    MPE_HIP(d_x.reserve(n_mp)); MPE_HIP(d_y.reserve(n_mp)); MPE_HIP(d_u.reserve(n_mp)); MPE_HIP(d_txo.reserve(n_mp)); MPE_HIP(d_tyo.reserve(n_mp));
+    MPE_HIP(d_member.reserve(n_mp));
+    if (n_mp) {
+        MPE_HIP(hipMemcpy(d_x.p, x, n_mp * sizeof(double), hipMemcpyHostToDevice));
+        MPE_HIP(hipMemcpy(d_y.p, y, n_mp * sizeof(double), hipMemcpyHostToDevice));
+        MPE_HIP(hipMemcpy(d_u.p, u, n_mp * sizeof(double), hipMemcpyHostToDevice));
+        MPE_HIP(hipMemcpy(d_txo.p, to_xo, n_mp * sizeof(int32_t), hipMemcpyHostToDevice));
+        MPE_HIP(hipMemcpy(d_tyo.p, to_yo, n_mp * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    if (const int rc = cluster_batch_on_device(params, prob_off, n_problems, d_x.p, d_y.p, d_u.p, d_txo.p, d_tyo.p, n_clusters, d_member.p, status, timing))
+        return rc;
+    if (n_mp) MPE_HIP(hipMemcpy(member, d_member.p, n_mp * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return DSA_OK;
+}
+
+extern "C" int mpe_cluster_batch_device(int device, const mpe_params* params, const int64_t* prob_off, int32_t n_problems,
+                                        const double* x, const double* y, const double* u, const int32_t* to_xo,
+                                        const int32_t* to_yo, int32_t* n_clusters, uint16_t* member, int32_t* status,
+                                        mpe_timing* timing)
+{
+    if (const int rc = check_batch(device, params, prob_off, n_problems)) return rc;
+    if (n_problems == 0) { if (timing) *timing = mpe_timing{}; return DSA_OK; }
+    if (prob_off[n_problems] && (!x || !y || !u || !to_xo || !to_yo || !member)) { g_mpe_err = "bad arguments"; return DSA_E_ARG; }
+    // whatever stream produced the arrays: all work on the device is over before the EM's own streams start
+    MPE_HIP(hipDeviceSynchronize());
+    return cluster_batch_on_device(params, prob_off, n_problems, x, y, u, to_xo, to_yo, n_clusters, member, status, timing);
 }
 
 extern "C" int mpe_cluster_batch_sharded(const int* devices, int32_t n_devices, const mpe_params* params, const int64_t* prob_off,

@@ -74,6 +74,79 @@ int  cmp_bin_fetch(cmp_binner* b, uint64_t* keys, int64_t* off_first, int64_t* o
 int  cmp_bin_fetch_part(cmp_binner* b, int which, int64_t from, int64_t n, cmp_packed* out);
 const char* cmp_last_error(void);
 
+/* ---- The EM problems of the bin pairs, built on the device ---------------------------------------------------------
+ *
+ * What the tool's host stages do between the bin pairs and MatePairEM (tools/clustermatepairs.cpp:478-545 with :292-375),
+ * for all bin pairs at once and with the same result bit for bit: bin pairs whose two lists both hold at least
+ * min_cluster_size entries are candidates; per side the entries of a candidate are grouped by fragment (fragments
+ * ascending as signed int, list order inside a fragment, wherever in the list its entries lie); fragments absent from the
+ * other side go (FilterUnmatched); per fragment an alignment is kept only if no alignment kept before it, of the same read
+ * end, reaches one of its minFusionRange bins (FilterOverlapping; bins by C++ truncating division); a bin pair with at
+ * least min_cluster_size matched fragments is a problem.  Its mate pairs are, fragment by fragment, the kept alignments of
+ * `first` in list order times those of `second` in list order (GetAlignPairs); per mate pair x = r1.end, y = r2.end,
+ * u = (fragment_mean - len1) - len2 on the strand-remapped regions, and to_xo / to_yo the rank inside the problem by x
+ * (y) descending, ties by index ascending — the arrays mpe_cluster_batch takes.  Problems come in ascending key order.
+ *
+ * Limits (DSA_E_LIMIT): a problem of more than INT32_MAX mate pairs, or more than INT32_MAX mate pairs in one build. */
+typedef struct cmp_problem_counts {
+    int64_t n_candidates;       /* bin pairs with both lists >= min_cluster_size */
+    int64_t n_problems, n_mate_pairs;
+    float   device_ms;          /* kernels, sorts and scans, HIP events */
+    float   pad_;
+} cmp_problem_counts;
+
+/* alignPairs: indices into the `first` and the `second` list of the problem's bin pair */
+typedef struct cmp_pair { int32_t first, second; } cmp_pair;
+
+/* One printed cluster member (OutputClusterMember, tools/clustermatepairs.cpp:549-583): index 0 = the alignment of
+ * `first` (cluster end 0), 1 = that of `second`.  ref is the reference index of the records, strand 0 plus / 1 minus. */
+typedef struct cmp_row {
+    int32_t cluster_id;
+    int32_t fragment[2], read_end[2], ref[2], strand[2], start[2], end[2];
+} cmp_row;
+
+/* the arrays on the device (device pointers; valid until the next build on the object or its destruction) */
+typedef struct cmp_problems_device {
+    const int64_t*  prob_off;   /* n_problems + 1 */
+    const double    *x, *y, *u; /* n_mate_pairs each */
+    const int32_t   *to_xo, *to_yo;
+    const cmp_pair* pairs;
+    const int32_t*  bin_pair;   /* n_problems: the index of the problem's bin pair among the keys */
+    uint16_t*       member;     /* room for n_mate_pairs masks: where mpe_cluster_batch_device may write, for cmp_problems_select */
+    int64_t n_problems, n_mate_pairs;
+    int32_t device, pad_;
+} cmp_problems_device;
+
+typedef struct cmp_problems cmp_problems;
+int  cmp_problems_create(cmp_problems** out, int device);
+void cmp_problems_destroy(cmp_problems* p);
+/* From what cmp_bin_run left on the binner's device (no cmp_bin_fetch needed).  The lists are read in place, also by
+ * cmp_problems_select afterwards: the binner has to stay alive, and unchanged, as long as this object is used.  The
+ * binner and the object must be on the same device. */
+int  cmp_problems_build(cmp_problems* p, cmp_binner* b, int32_t min_fusion_range, int32_t min_cluster_size, double fragment_mean,
+                        cmp_problem_counts* counts);
+/* The same from lists in host memory, in the layout cmp_bin_fetch hands out (keys ascending and distinct, n_keys + 1
+ * offsets per side): they are uploaded and go through the same kernels. */
+int  cmp_problems_build_lists(cmp_problems* p, const uint64_t* keys, const int64_t* off_first, const int64_t* off_second,
+                              const cmp_packed* first, const cmp_packed* second, int64_t n_keys, int32_t min_fusion_range,
+                              int32_t min_cluster_size, double fragment_mean, cmp_problem_counts* counts);
+/* Any subset of the arrays to the host (NULL = not wanted); sizes as in cmp_problems_device. */
+int  cmp_problems_fetch(cmp_problems* p, int64_t* prob_off, double* x, double* y, double* u, int32_t* to_xo, int32_t* to_yo,
+                        cmp_pair* pairs, int32_t* bin_pair);
+/* The build has completed on the device when cmp_problems_build* returns: the pointers can be used from any stream. */
+int  cmp_problems_view(const cmp_problems* p, cmp_problems_device* out);
+/* The lines to print of problems [p0, p1), chosen on the device.  n_clusters (host) holds p1 - p0 counts, n_clusters[0]
+ * that of problem p0; member (DEVICE pointer) holds the masks of their mate pairs, member[0] that of mate pair
+ * prob_off[p0] — what mpe_cluster_batch_device wrote.  For cluster j < n_clusters[p] a mate pair is selected when its bit
+ * j is set and no earlier mate pair of the same fragment in that problem has bit j set; bits from n_clusters[p] up are
+ * ignored.  Rows come by problem, then cluster, then mate pair; cluster_id = cluster_base + (sum of n_clusters of the
+ * problems of the range before p) + j.  The rows stay on the device until the next select; *n_rows receives their number. */
+int  cmp_problems_select(cmp_problems* p, int64_t p0, int64_t p1, const int32_t* n_clusters, const uint16_t* member,
+                         int32_t cluster_base, int64_t* n_rows);
+/* The rows of the last select.  *n_rows always receives their number; DSA_E_CAPACITY if cap is short (nothing is copied,
+ * rows may then be NULL). */
+int  cmp_problems_rows(cmp_problems* p, cmp_row* rows, int64_t cap, int64_t* n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,14 @@ int mpe_cluster_batch(int device, const mpe_params* params, const int64_t* prob_
 int mpe_cluster_batch_sharded(const int* devices, int32_t n_devices, const mpe_params* params, const int64_t* prob_off,
                               int32_t n_problems, const double* x, const double* y, const double* u, const int32_t* to_xo,
                               const int32_t* to_yo, int32_t* n_clusters, uint16_t* member, int32_t* status, mpe_timing* timing);
+/* mpe_cluster_batch with x, y, u, to_xo, to_yo as DEVICE pointers on `device` (what cmp_problems_view of include/defuse_cmp.h hands
+ * out) and member written to a DEVICE pointer (n_mate_pairs masks, for cmp_problems_select); prob_off, n_clusters, status
+ * and timing stay in host memory.  After the uploads both entries run the same code.  The EM runs on streams of its own:
+ * this entry synchronises the device (hipDeviceSynchronize) before it starts, so the arrays may come from any stream; the
+ * masks are complete when it returns. */
+int mpe_cluster_batch_device(int device, const mpe_params* params, const int64_t* prob_off, int32_t n_problems,
+                             const double* x, const double* y, const double* u, const int32_t* to_xo, const int32_t* to_yo,
+                             int32_t* n_clusters, uint16_t* member, int32_t* status, mpe_timing* timing);
 const char* mpe_last_error(void);
 
 #ifdef __cplusplus

@@ -4,7 +4,8 @@
 // bucketing of all fragments (tools/clustermatepairs.cpp:146-290) run on the GPU through include/defuse_cmp.h (one
 // thread per fragment, a stable radix sort by bin-pair key in place of the reference's hash map); the per-bin-pair
 // filters and the output (:292-375,478-584) are host code; MatePairEM::DoClustering for all bin pairs runs on the
-// GPU in batches through include/defuse_mpe.h.  No CPU fallback: DEFUSE_CMP_HOST_BINNING=1 selects the host
+// GPU in batches through include/defuse_mpe.h.  DEFUSE_CMP_DEVICE_PROBLEMS=1 (opt-in) moves the per-bin-pair filters and the choice
+// of the lines to print to the GPU as well (cmp_problems_* of include/defuse_cmp.h): no list leaves the device.  No CPU fallback: DEFUSE_CMP_HOST_BINNING=1 selects the host
 // transcription of the bucketing as a cross-check (tests compare the two), it is never taken by itself.
 // Iteration orders the reference leaves to boost::unordered_map are the canonical ascending-key
 // orders of SURVEY.md 8(c).
@@ -186,6 +187,30 @@ int main(int argc, char* argv[])
         _exit(1);
     };
     const bool host_binning = [] { const char* e = std::getenv("DEFUSE_CMP_HOST_BINNING"); return e && std::atoi(e) != 0; }();
+    // DEFUSE_GPUS = "all", a count, or a list of device ordinals: the bin pairs are shared out over those GPUs
+    // (bin pairs are independent, SURVEY 8(e)); otherwise one GPU as for every tool (DEFUSE_GPU / lock files)
+    auto devices_from_env = [] {
+        std::vector<int> devs;
+        if (const char* g = std::getenv("DEFUSE_GPUS")) {
+            const std::string spec = g;
+            const int have = dsa_device_count();
+            if (spec == "all") for (int d = 0; d < have; ++d) devs.push_back(d);
+            else if (spec.find(',') != std::string::npos) for (const std::string& f : split_tabs(spec, ',')) devs.push_back(std::atoi(f.c_str()));
+            else for (int d = 0; d < std::atoi(spec.c_str()); ++d) devs.push_back(have > 0 ? d % have : d);
+        }
+        return devs;
+    };
+    // DEFUSE_CMP_DEVICE_PROBLEMS=1: the EM problems are built on the device from the bin pairs where cmp_bin_run left them, the
+    // EM reads them there and the lines to print are chosen there (include/defuse_cmp.h, cmp_problems_*): no list comes down.
+    // The host stages below stay the default and the yardstick; they also serve the host cross-check of the binning, several
+    // devices (the shares of mpe_cluster_batch_sharded take host arrays) and DEFUSE_CMP_DUMP_PROBLEMS (a dump of the host stages).
+    bool device_problems = [] { const char* e = std::getenv("DEFUSE_CMP_DEVICE_PROBLEMS"); return e && std::atoi(e) != 0; }();
+    auto keep_host_path = [&](const char* why) {
+        if (timing) std::cerr << "[clustermatepairs] DEFUSE_CMP_DEVICE_PROBLEMS: stays on the host path (" << why << ")" << std::endl;
+        device_problems = false;
+    };
+    if (device_problems && host_binning) keep_host_path("DEFUSE_CMP_HOST_BINNING=1");
+    if (device_problems && std::getenv("DEFUSE_CMP_DUMP_PROBLEMS")) keep_host_path("DEFUSE_CMP_DUMP_PROBLEMS dumps the host stages");
     int gpu_device = -1;                                                      // the device of this process's first GPU call
     cmp_binner* binner = nullptr;
     int binner_rc = DSA_OK;
@@ -353,6 +378,8 @@ int main(int argc, char* argv[])
     struct Joined { std::vector<uint64_t> key; std::vector<PackedPair> store; };
     std::vector<Joined> joined(host_binning ? nThreads : 0);                  // owner of the lists (host path)
     std::unique_ptr<AlignmentPacked[]> devFirst, devSecond;                   // owner of the lists (device path)
+    cmp_stats binStats{};                                                     // of cmp_bin_run
+    double t_binned = 0, t_first_em = 0;                                      // cmp_bin_run's return, the first EM call
     auto first_device = [&] {
         if (binner_thread.joinable()) binner_thread.join();
         if (gpu_device < 0) gpu_device = dsa_pick_device();
@@ -516,8 +543,9 @@ int main(int argc, char* argv[])
         for (int rc : rcs)
             if (rc != DSA_OK) die(std::string("Error: bin pairs on the GPU failed: ") + cmp_last_error());
         stage("  records on the device");
-        cmp_stats st{};
+        cmp_stats& st = binStats;
         if (cmp_bin_run(binner, minFusionRange, &st) != DSA_OK) die(std::string("Error: bin pairs on the GPU failed: ") + cmp_last_error());
+        t_binned = now();
         if (st.err_record >= 0) {
             // the alignment on which the reference stops (:178-192 DebugChecks, :28-65 packing limits): its message and exit
             unsigned t = 0;
@@ -529,25 +557,33 @@ int main(int argc, char* argv[])
             std::cout << (refs ? (int)(a.meta & 0x0FFFFFFFu) : std::max(startBin, 1 << 13)) << std::endl << (refs ? (1 << 18) : (1 << 13)) << std::endl;
             die(refs ? "Packing failed, too many reference sequences" : "Packing failed, chromosome too large");
         }
-        std::vector<int64_t> off1((size_t)st.n_keys + 1), off2((size_t)st.n_keys + 1);
-        binPairKey.resize((size_t)st.n_keys);
-        devFirst.reset(new AlignmentPacked[(size_t)st.n_first + 1]);              // (not value-initialised: every thread touches its own share first)
-        devSecond.reset(new AlignmentPacked[(size_t)st.n_second + 1]);
-        if (cmp_bin_fetch(binner, binPairKey.data(), off1.data(), off2.data(), nullptr, nullptr) != DSA_OK)
-            die(std::string("Error: bin pairs on the GPU failed: ") + cmp_last_error());
-        run_threads([&](unsigned t) {
-            const int64_t a0 = st.n_first * t / nThreads, a1 = st.n_first * (t + 1) / nThreads;
-            const int64_t b0 = st.n_second * t / nThreads, b1 = st.n_second * (t + 1) / nThreads;
-            rcs[t] = cmp_bin_fetch_part(binner, 0, a0, a1 - a0, (cmp_packed*)devFirst.get() + a0);
-            if (rcs[t] == DSA_OK) rcs[t] = cmp_bin_fetch_part(binner, 1, b0, b1 - b0, (cmp_packed*)devSecond.get() + b0);
-        });
-        for (int rc : rcs)
-            if (rc != DSA_OK) die(std::string("Error: bin pairs on the GPU failed: ") + cmp_last_error());
-        cmp_bin_destroy(binner);
-        binPairStore.resize((size_t)st.n_keys);
-        for (size_t k = 0; k < (size_t)st.n_keys; ++k)
-            binPairStore[k] = PairView{ListView{devFirst.get() + off1[k], (size_t)(off1[k + 1] - off1[k])},
-                                       ListView{devSecond.get() + off2[k], (size_t)(off2[k + 1] - off2[k])}};
+        if (device_problems) {
+            std::vector<int> devs = devices_from_env();
+            std::sort(devs.begin(), devs.end());
+            if (std::unique(devs.begin(), devs.end()) - devs.begin() > 1) keep_host_path("DEFUSE_GPUS names more than one device");
+        }
+        // the host stages take the lists from host memory; with device_problems they stay where they are, and the binner with them
+        if (!device_problems) {
+            std::vector<int64_t> off1((size_t)st.n_keys + 1), off2((size_t)st.n_keys + 1);
+            binPairKey.resize((size_t)st.n_keys);
+            devFirst.reset(new AlignmentPacked[(size_t)st.n_first + 1]);              // (not value-initialised: every thread touches its own share first)
+            devSecond.reset(new AlignmentPacked[(size_t)st.n_second + 1]);
+            if (cmp_bin_fetch(binner, binPairKey.data(), off1.data(), off2.data(), nullptr, nullptr) != DSA_OK)
+                die(std::string("Error: bin pairs on the GPU failed: ") + cmp_last_error());
+            run_threads([&](unsigned t) {
+                const int64_t a0 = st.n_first * t / nThreads, a1 = st.n_first * (t + 1) / nThreads;
+                const int64_t b0 = st.n_second * t / nThreads, b1 = st.n_second * (t + 1) / nThreads;
+                rcs[t] = cmp_bin_fetch_part(binner, 0, a0, a1 - a0, (cmp_packed*)devFirst.get() + a0);
+                if (rcs[t] == DSA_OK) rcs[t] = cmp_bin_fetch_part(binner, 1, b0, b1 - b0, (cmp_packed*)devSecond.get() + b0);
+            });
+            for (int rc : rcs)
+                if (rc != DSA_OK) die(std::string("Error: bin pairs on the GPU failed: ") + cmp_last_error());
+            cmp_bin_destroy(binner);
+            binPairStore.resize((size_t)st.n_keys);
+            for (size_t k = 0; k < (size_t)st.n_keys; ++k)
+                binPairStore[k] = PairView{ListView{devFirst.get() + off1[k], (size_t)(off1[k + 1] - off1[k])},
+                                           ListView{devSecond.get() + off2[k], (size_t)(off2[k + 1] - off2[k])}};
+        }
         if (timing)
             std::cerr << "[clustermatepairs]   bin pairs on the device: " << st.n_fragments << " fragments, " << st.n_concordant << " concordant, " << st.n_keys
                       << " bin pairs, " << st.n_first + st.n_second << " entries, kernels + sorts " << st.device_ms << " ms" << std::endl;
@@ -569,6 +605,158 @@ int main(int argc, char* argv[])
     if (!out.open_file(cmd.str("clusters"))) die("Error: unable to write to clusters file");
 
     std::cout << "Creating clusters" << std::endl;
+    // the end of both paths
+    auto finish = [&](int nClusters) {
+        if (!out.close_file()) die("Error: failed writing the clusters file");
+        // (on both paths, so that they can be compared: from cmp_bin_run's return, i.e. fetch + first chunk's problems on the host path)
+        if (timing && t_binned > 0 && t_first_em > 0)
+            std::cerr << "[clustermatepairs]   bin pairs on the device to the first EM call: " << (t_first_em - t_binned) << " s" << std::endl;
+        stage("problems + clustering + output");
+        std::cout << "Created " << nClusters << " clusters" << std::endl;
+        // The clusters file is complete and closed.  The process ends here without destroying its tables one by one (gigabytes in
+        // millions of blocks at full size: more than a second of the round-3 tool's 8.9 s) and without the GPU runtime's own
+        // shutdown; the system takes all of it back at once.
+        std::cout.flush();
+        std::cerr.flush();
+        fflush(nullptr);
+        if (std::getenv("DEFUSE_FULL_EXIT")) exit(0);      // under a profiler that writes its files at exit (rocprofv3): atexit handlers run
+        _exit(0);
+    };
+    if (device_problems) {
+        // The device path: the problems of all bin pairs are built on the device in one go; the EM takes them there, range of
+        // problems by range (the chunks: about equal mate pair counts), and writes the member masks there; the lines to print are
+        // chosen there and come down as rows, which host threads format.  The GPU thread clusters chunk c + 1 while the writer
+        // selects, formats and writes chunk c.  Cluster ids are a running count, so the file does not depend on the cut.
+        const int device = first_device();
+        const double t0 = now();
+        cmp_problems* probs = nullptr;
+        cmp_problem_counts pcnt{};
+        cmp_problems_device view{};
+        if (cmp_problems_create(&probs, device) != DSA_OK || cmp_problems_build(probs, binner, minFusionRange, minClusterSize, fragmentMean, &pcnt) != DSA_OK ||
+            cmp_problems_view(probs, &view) != DSA_OK)
+            die(std::string("Error: problems on the GPU failed: ") + cmp_last_error());
+        const size_t nProblems = (size_t)pcnt.n_problems;
+        std::vector<int64_t> probOff(nProblems + 1);
+        if (cmp_problems_fetch(probs, probOff.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != DSA_OK)
+            die(std::string("Error: problems on the GPU failed: ") + cmp_last_error());
+        double t_build = now() - t0, t_cluster = 0, t_write = 0;
+        if (timing)
+            std::cerr << "[clustermatepairs]   problems on the device: " << pcnt.n_candidates << " candidate bin pairs, " << pcnt.n_problems << " problems, "
+                      << pcnt.n_mate_pairs << " mate pairs, kernels + sorts " << pcnt.device_ms << " ms" << std::endl;
+        if (std::getenv("DEFUSE_CMP_DUMP_EM")) {                               // test aid: exactly the arrays the EM receives, then stop
+            stage("problems");
+            const size_t n = (size_t)pcnt.n_mate_pairs;
+            std::vector<double> X(n), Y(n), U(n);
+            std::vector<int32_t> toXO(n), toYO(n);
+            if (cmp_problems_fetch(probs, nullptr, X.data(), Y.data(), U.data(), toXO.data(), toYO.data(), nullptr, nullptr) != DSA_OK)
+                die(std::string("Error: problems on the GPU failed: ") + cmp_last_error());
+            std::ofstream d(std::getenv("DEFUSE_CMP_DUMP_EM"), std::ios::binary);
+            const int64_t head[2] = {(int64_t)nProblems, (int64_t)n};
+            auto put = [&](const void* p, size_t bytes) { d.write((const char*)p, (std::streamsize)bytes); };
+            put(head, sizeof(head));
+            put(&prm, sizeof(prm));
+            put(probOff.data(), probOff.size() * sizeof(int64_t));
+            put(X.data(), n * sizeof(double)); put(Y.data(), n * sizeof(double)); put(U.data(), n * sizeof(double));
+            put(toXO.data(), n * sizeof(int32_t)); put(toYO.data(), n * sizeof(int32_t));
+            cmp_problems_destroy(probs);
+            cmp_bin_destroy(binner);
+            return d.good() ? 0 : 1;
+        }
+        unsigned nChunks = (size_t)(binStats.n_first + binStats.n_second) >= ((size_t)8 << 20) ? 4u : 1u;
+        if (const char* e = std::getenv("DEFUSE_CMP_CHUNKS")) nChunks = (unsigned)std::max(1, std::atoi(e));
+        nChunks = (unsigned)std::min<size_t>(nChunks, std::max<size_t>(1, nProblems));
+        std::vector<size_t> chunkCut(nChunks + 1, nProblems);                  // ranges of problems of about equal mate pair count
+        chunkCut[0] = 0;
+        for (unsigned c = 1; c < nChunks; ++c) {
+            const int64_t want = probOff[nProblems] / nChunks * c;
+            const size_t at = (size_t)(std::lower_bound(probOff.begin(), probOff.end(), want) - probOff.begin());
+            chunkCut[c] = std::min(std::max(at, chunkCut[c - 1]), nProblems);
+        }
+        std::vector<int32_t> nClusters(nProblems, 0);
+        mpe_timing tsum{};
+        auto cluster_range = [&](size_t lo, size_t hi) {                        // problems [lo, hi): the EM where the arrays are
+            if (lo == hi) return;
+            if (hi - lo > (size_t)INT32_MAX) die("Error: more than 2^31 - 1 bin pairs in one chunk (raise DEFUSE_CMP_CHUNKS)");
+            const int64_t base = probOff[lo];
+            std::vector<int64_t> off(hi - lo + 1);
+            for (size_t p = lo; p <= hi; ++p) off[p - lo] = probOff[p] - base;
+            std::vector<int32_t> status(hi - lo, 0);
+            mpe_timing t;
+            if (t_first_em == 0) t_first_em = now();
+            const int rc = mpe_cluster_batch_device(device, &prm, off.data(), (int32_t)(hi - lo), view.x + base, view.y + base, view.u + base,
+                                                    view.to_xo + base, view.to_yo + base, nClusters.data() + lo, view.member + base, status.data(), &t);
+            if (rc != 0) die(std::string("Error: mate pair clustering on the GPU failed: ") + mpe_last_error());
+            tsum.kernel_ms += t.kernel_ms; tsum.n_problems += t.n_problems; tsum.n_mate_pairs += t.n_mate_pairs;
+            tsum.em_iterations += t.em_iterations; tsum.n_wave_problems += t.n_wave_problems;
+            for (int32_t st : status)
+                if (st) die("Error: a consistency check of the mate pair clusterer failed (DebugCheck in the reference)");
+        };
+        // output (:549-583): the rows of a round of problems come down in print order; every host thread formats a contiguous share
+        int clusterID = 0;
+        std::vector<cmp_row> rows;
+        auto write_range = [&](size_t cLo, size_t cHi) {
+            for (size_t lo = cLo; lo < cHi;) {                   // rounds of about four million mate pairs bound the rows and the text held in memory
+                size_t hi = lo;
+                while (hi < cHi && probOff[hi] - probOff[lo] < (1 << 22)) ++hi;
+                int64_t nRows = 0;
+                if (cmp_problems_select(probs, (int64_t)lo, (int64_t)hi, nClusters.data() + lo, view.member + probOff[lo], clusterID, &nRows) != DSA_OK)
+                    die(std::string("Error: cluster rows on the GPU failed: ") + cmp_last_error());
+                rows.resize((size_t)nRows);
+                if (cmp_problems_rows(probs, rows.data(), nRows, &nRows) != DSA_OK) die(std::string("Error: cluster rows on the GPU failed: ") + cmp_last_error());
+                for (size_t p = lo; p < hi; ++p) clusterID += nClusters[p];
+                std::vector<std::string> texts(nThreads);
+                run_threads([&](unsigned t) {
+                    std::string& buf = texts[t];
+                    auto put_int = [&](int v) {
+                        char tmp[16];
+                        buf.append(tmp, (size_t)(defuse::put_int(tmp, v) - tmp));
+                    };
+                    for (size_t r = rows.size() * t / nThreads; r < rows.size() * (t + 1) / nThreads; ++r) {
+                        const cmp_row& row = rows[r];
+                        for (int ce = 0; ce <= 1; ++ce) {
+                            put_int(row.cluster_id); buf += '\t'; put_int(ce); buf += '\t'; put_int(row.fragment[ce]); buf += '\t'; put_int(row.read_end[ce]);
+                            buf += '\t'; buf += refNames[(size_t)row.ref[ce]]; buf += '\t'; buf += (row.strand[ce] == PlusStrand ? '+' : '-'); buf += '\t';
+                            put_int(row.start[ce]); buf += '\t'; put_int(row.end[ce]); buf += '\n';
+                        }
+                    }
+                });
+                out.write_round_async(std::move(texts), nThreads);      // copied into the file while the next round is selected and formatted
+                lo = hi;
+            }
+        };
+        {
+            std::mutex mu;
+            std::condition_variable cv;
+            std::vector<char> clustered(nChunks, 0);
+            std::thread writer([&] {
+                for (unsigned c = 0; c < nChunks; ++c) {
+                    {
+                        std::unique_lock<std::mutex> lk(mu);
+                        cv.wait(lk, [&] { return clustered[c] != 0; });
+                    }
+                    const double t1 = now();
+                    write_range(chunkCut[c], chunkCut[c + 1]);
+                    t_write += now() - t1;
+                }
+            });
+            for (unsigned c = 0; c < nChunks; ++c) {
+                const double t1 = now();
+                cluster_range(chunkCut[c], chunkCut[c + 1]);
+                t_cluster += now() - t1;
+                { std::lock_guard<std::mutex> lk(mu); clustered[c] = 1; }
+                cv.notify_all();
+            }
+            writer.join();
+        }
+        if (timing) {
+            std::cerr << "[clustermatepairs] " << tsum.n_problems << " bin pairs, " << tsum.n_mate_pairs << " mate pairs, " << tsum.em_iterations
+                      << " EM iterations, " << tsum.n_wave_problems << " bin pairs with a wave each, 1 device share(s), kernel " << tsum.kernel_ms << " ms"
+                      << std::endl;
+            std::cerr << "[clustermatepairs] " << nChunks << " chunk(s), stages overlapped: problems " << t_build << " s, clustering " << t_cluster
+                      << " s, output " << t_write << " s" << std::endl;
+        }
+        finish(clusterID);
+    }
     // per bin pair: unpack, match fragments, drop overlapping alignments, enumerate alignment pairs (:478-545)
     std::vector<uint32_t> bpOrder(binPairKey.size());
     std::iota(bpOrder.begin(), bpOrder.end(), 0u);
@@ -690,24 +878,17 @@ int main(int argc, char* argv[])
     }
     };
 
-    // DEFUSE_GPUS = "all", a count, or a list of device ordinals: the bin pairs are shared out over those GPUs
-    // (bin pairs are independent, SURVEY 8(e)); otherwise one GPU as for every tool (DEFUSE_GPU / lock files)
-    std::vector<int> devices;
+    std::vector<int> devices;                       // of DEFUSE_GPUS (devices_from_env), else this process's one GPU
     mpe_timing tsum{};
     auto cluster_chunk = [&](Chunk& ck) {
         ck.nClusters.assign(ck.problems.size(), 0);
         ck.member.assign(ck.X.size(), 0);
         if (ck.problems.empty()) return;
         if (devices.empty()) {
-            if (const char* g = std::getenv("DEFUSE_GPUS")) {
-                const std::string spec = g;
-                const int have = dsa_device_count();
-                if (spec == "all") for (int d = 0; d < have; ++d) devices.push_back(d);
-                else if (spec.find(',') != std::string::npos) for (const std::string& f : split_tabs(spec, ',')) devices.push_back(std::atoi(f.c_str()));
-                else for (int d = 0; d < std::atoi(spec.c_str()); ++d) devices.push_back(have > 0 ? d % have : d);
-            }
+            devices = devices_from_env();
             if (devices.empty()) devices.push_back(first_device());
         }
+        if (t_first_em == 0) t_first_em = now();
         std::vector<int32_t> status(ck.problems.size(), 0);
         mpe_timing t;
         const int rc = mpe_cluster_batch_sharded(devices.data(), (int32_t)devices.size(), &prm, ck.probOff.data(), (int32_t)ck.problems.size(),
@@ -860,15 +1041,5 @@ int main(int argc, char* argv[])
                       << " s, output " << t_write << " s" << std::endl;
         }
     }
-    if (!out.close_file()) die("Error: failed writing the clusters file");
-    stage("problems + clustering + output");
-    std::cout << "Created " << clusterID << " clusters" << std::endl;
-    // The clusters file is complete and closed.  The process ends here without destroying its tables one by one (gigabytes in
-    // millions of blocks at full size: more than a second of the round-3 tool's 8.9 s) and without the GPU runtime's own
-    // shutdown; the system takes all of it back at once.
-    std::cout.flush();
-    std::cerr.flush();
-    fflush(nullptr);
-    if (std::getenv("DEFUSE_FULL_EXIT")) exit(0);      // under a profiler that writes its files at exit (rocprofv3): atexit handlers run
-    _exit(0);
+    finish(clusterID);
 }
