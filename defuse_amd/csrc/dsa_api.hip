@@ -63,7 +63,7 @@ struct PipeLane {
     unsigned tier_hint = 0xFu;  // fill kernels the lane's last slice needed (bit t: k_fill_fast<t>, bit 3: k_fill_generic): the ones launched
     unsigned tiers_launched = 0;    // ... for the slice in flight
     DevBuf<uint8_t> d_wg_tier;  // which fill kernel owns each workgroup (written by k_fill_fast<0>)
-    DevBuf<uint32_t> d_rowcodes, d_rowbytes, d_bnd, d_cmax, d_rmax, d_tmask;
+    DevBuf<uint32_t> d_rowcodes, d_rowbytes, d_bnd, d_cmax, d_rmax;
     DevBuf<PairState> d_state;
     DevBuf<KeptRow> d_kept;
     DevBuf<int64_t> d_rec_count, d_rec_offset;
@@ -212,7 +212,7 @@ void for_each_tile_width(Fn&& fn)
 size_t slice_scratch_bytes(int64_t n_waves, int lq1, int nch)
 {
     size_t rows = (size_t)n_waves * lq1 * WAVE * 4;
-    return 3 * rows + rows / 4 + 2 * rows * (size_t)nch;      // rowcodes, rmax, tmask; the byte plane of the table sweeps; bnd, cmax
+    return 2 * rows + rows / 4 + 2 * rows * (size_t)nch;      // rowcodes, rmax; the byte plane of the table sweeps; bnd, cmax
 }
 
 // Slices bound the scratch footprint: contiguous ranges of the caller's pair order that fit the budget (and
@@ -442,14 +442,14 @@ int launch_compute(dsa_ctx* ctx, PipeLane& L, const Slice& s)
         launched = true;
 #define DSA_LAUNCH_FILL(TIER)                                                                                                                    \
     hipLaunchKernelGGL((k_fill_fast<TIER, WIDE, WT>), dim3((unsigned)g.n_wgs), dim3(WG_LANES), 0, st, pairs, L.d_wg_tier.p, ctx->d_refcodes.p, \
-                       ctx->d_reads.p, L.d_rowcodes.p, L.d_rowbytes.p, ctx->d_min_score.p, ctx->d_fusions.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, L.d_tmask.p, fb, g)
+                       ctx->d_reads.p, L.d_rowcodes.p, L.d_rowbytes.p, ctx->d_min_score.p, ctx->d_fusions.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, fb, g)
         DSA_LAUNCH_FILL(0);
         if (mask & 2u) DSA_LAUNCH_FILL(1);
         if (mask & 4u) DSA_LAUNCH_FILL(2);
 #undef DSA_LAUNCH_FILL
         if (mask & 8u)
             hipLaunchKernelGGL((k_fill_generic<WT>), dim3((unsigned)g.n_wgs), dim3(WG_LANES), 0, st, pairs, ctx->d_fusions.p, L.d_wg_tier.p, ctx->d_refcodes.p,
-                               ctx->d_reads.p, L.d_rowcodes.p, ctx->d_min_score.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, L.d_tmask.p, fb, g);
+                               ctx->d_reads.p, L.d_rowcodes.p, ctx->d_min_score.p, L.d_bnd.p, L.d_cmax.p, L.d_rmax.p, fb, g);
     };
     for_each_tile_width([&](auto wt_c) {
         launch_fills(wt_c, std::false_type{});
@@ -496,7 +496,6 @@ int phase1(dsa_ctx* ctx, PipeLane& L, int slice_idx)
     HIPC(L.d_bnd.reserve(n_rows * g.nch));
     HIPC(L.d_cmax.reserve(n_rows * g.nch));
     HIPC(L.d_rmax.reserve(n_rows));
-    HIPC(L.d_tmask.reserve(n_rows));
     HIPC(L.d_tstop.reserve((size_t)g.n_waves * g.nch));
     HIPC(L.d_state.reserve(np));
     HIPC(L.d_rec_count.reserve(np + 1));

@@ -515,7 +515,7 @@ __device__ __forceinline__ int nth_set_bit(uint64_t m, int n)   // index of the 
 // comes from device cursors (capacities are checked by the host afterwards).  The first tile pair of
 // every pair is offered to the table-driven replay: per fusion of the workgroup the first offer fixes
 // the (M1 tile, M2 tile) the tables will be built for.
-constexpr int TMASK_TILES = 16;   // tmask covers references of at most 16 tiles
+struct TileStops { int v[8]; };    // stored row groups of a wave's first tiles (wave-uniform; 0 past the wave's last tile)
 
 // device buffers of the finish stage and their capacities, handed to the fill and the finish kernels as one argument
 struct FinishBufs {
@@ -575,27 +575,27 @@ struct FinishLds {
     uint64_t kc[KCACHE * WG_LANES];    // [k][thread], a KeptRow each
 };
 
-// four wave-aggregated allocations at once: the four atomics are in flight together
-__device__ __forceinline__ void wave_alloc4(Counters* ctr, const unsigned (&n)[4], unsigned long long (&base)[4])
+// three wave-aggregated allocations at once: the three atomics are in flight together
+__device__ __forceinline__ void wave_alloc3(Counters* ctr, const unsigned (&n)[3], unsigned long long (&base)[3])
 {
-    unsigned incl[4] = {n[0], n[1], n[2], n[3]};
+    unsigned incl[3] = {n[0], n[1], n[2]};
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < 3; ++q) {
             const unsigned y = __shfl_up(incl[q], d, 64);
             if ((int)(threadIdx.x & 63) >= d) incl[q] += y;
         }
     }
-    unsigned long long* const counter[4] = {&ctr->n_kept, &ctr->n_tasks, &ctr->n_masks, &ctr->n_gtasks};
-    unsigned long long b[4] = {0, 0, 0, 0};
+    unsigned long long* const counter[3] = {&ctr->n_tasks, &ctr->n_masks, &ctr->n_gtasks};
+    unsigned long long b[3] = {0, 0, 0};
     if ((threadIdx.x & 63) == 63) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+        for (int q = 0; q < 3; ++q)
             if (incl[q]) b[q] = atomicAdd(counter[q], (unsigned long long)incl[q]);
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) base[q] = __shfl(b[q], 63, 64) + (incl[q] - n[q]);
+    for (int q = 0; q < 3; ++q) base[q] = __shfl(b[q], 63, 64) + (incl[q] - n[q]);
 }
 
 // Runs in the workgroup that filled these pairs, right after its row maxima are written: every lane
@@ -605,7 +605,7 @@ __device__ __forceinline__ void wave_alloc4(Counters* ctr, const unsigned (&n)[4
 template <bool HANDOFF, int WT>
 __device__ __forceinline__ void combine_wg(
     const dsa_pair* __restrict__ pairs, const dsa_fusion* __restrict__ fusions, const uint32_t* __restrict__ cmax,
-    const uint32_t* __restrict__ rmax, const uint32_t* __restrict__ tmask, const int32_t* __restrict__ min_score_tab,
+    const uint32_t* __restrict__ rmax, const TileStops& stops, const int32_t* __restrict__ min_score_tab,
     const WgView& wgi, int my_group, bool fast_wg, FinishLds* fl, const FinishBufs& fb, const Geom& g)
 {
     PairState* __restrict__ state = fb.state;
@@ -621,7 +621,6 @@ __device__ __forceinline__ void combine_wg(
     if (tid < GSPLIT2) fl->tile[tid] = -1;
     const uint32_t* rm = rmax + w * g.lq1 * WAVE;
     const uint4* rm4 = reinterpret_cast<const uint4*>(rm) + lane;
-    const uint4* tm4 = reinterpret_cast<const uint4*>(tmask + w * g.lq1 * WAVE) + lane;
     // FindMaxRowEntry's acceptance rule (tools/SplitReadAligner.cpp:91-102): below minSplitScore counts as 0
     auto accept = [](uint32_t word, int h, int n_chunks, int row) -> int {
         if (row == 0 || n_chunks == 0) return 0;   // H(i,0)=0 < 8; empty reference: only column 0 (<=0)
@@ -648,106 +647,110 @@ __device__ __forceinline__ void combine_wg(
         nc1 = cdiv_dev(fu.ref1_len, WT);
         small = nc0 <= 64 && nc1 <= 64;
         const int min_score = min_score_tab[lq];
-        if (g.nch <= TMASK_TILES) {
-            // One pass over the read splits a, four per step: row maxima and winning-tile masks of the rows
-            // a and lq-a come from six dwordx4 loads, issued two steps ahead (no dependent round trips).
-            struct Step { uint4 x, yh, yl, tx, th, tl; };
-            const int ng = lq >> 2;
-            auto load = [&](int gq) -> Step {
-                gq = gq < ng ? gq : ng;
-                const int b_hi = lq - 4 * gq, b_lo = b_hi - 3;
-                const int64_t ih = (int64_t)(b_hi >> 2) * WAVE, il = (int64_t)((b_lo > 0 ? b_lo : 0) >> 2) * WAVE;
-                Step s;
-                s.x = rm4[(int64_t)gq * WAVE];
-                s.yh = rm4[ih];
-                s.yl = rm4[il];
-                s.tx = tm4[(int64_t)gq * WAVE];
-                s.th = tm4[ih];
-                s.tl = tm4[il];
-                return s;
-            };
-            Step s0 = load(0), s1 = load(1);
-            for (int gq = 0; gq <= ng; ++gq) {
-                const Step cur = s0;
-                s0 = s1;
-                s1 = load(gq + 2);
-                const int b_hi = lq - 4 * gq;
+        // One pass over the read splits a, four per step: the row maxima of the rows a and lq-a come from three
+        // dwordx4 loads, issued two steps ahead (no dependent round trips).
+        struct Step { uint4 x, yh, yl; };
+        const int ng = lq >> 2;
+        auto load = [&](int gq) -> Step {
+            gq = gq < ng ? gq : ng;
+            const int b_hi = lq - 4 * gq, b_lo = b_hi - 3;
+            Step s;
+            s.x = rm4[(int64_t)gq * WAVE];
+            s.yh = rm4[(int64_t)(b_hi >> 2) * WAVE];
+            s.yl = rm4[(int64_t)((b_lo > 0 ? b_lo : 0) >> 2) * WAVE];
+            return s;
+        };
+        Step s0 = load(0), s1 = load(1);
+        for (int gq = 0; gq <= ng; ++gq) {
+            const Step cur = s0;
+            s0 = s1;
+            s1 = load(gq + 2);
+            const int b_hi = lq - 4 * gq;
 #pragma unroll
-                for (int sidx = 0; sidx < 4; ++sidx) {
-                    const int a = 4 * gq + sidx, b = lq - a;
-                    if (b < 0) continue;
-                    const bool in_hi = (b >> 2) == (b_hi >> 2);
-                    const uint32_t yw = in_hi ? pick(cur.yh, b & 3) : pick(cur.yl, b & 3);
-                    const int m1 = accept(pick(cur.x, sidx), 0, nc0, a), m2 = accept(yw, 1, nc1, b);
-                    const int sc = m1 + m2;
-                    if (sc < min_score || sc < max_score) continue;
-                    if (sc > max_score) {        // a better split: forget the kept rows so far
-                        max_score = sc;
-                        n_kept = 0;
-                        tiles0 = tiles1 = 0;
-                    }
-                    if (m1 == 0 || m2 == 0) continue;   // an empty side emits nothing
-                    if (n_kept == 0) first_a = a;
-                    last_a = a;
-                    KeptRow kr;
-                    kr.a = (int16_t)a;
-                    kr.m1 = (int16_t)m1;
-                    kr.m2 = (int16_t)m2;
-                    kr.pad_ = 0;
-#pragma unroll
-                    for (int k = 0; k < KCACHE; ++k)
-                        if (n_kept == k) kcr[k] = __builtin_bit_cast(uint64_t, kr);
-                    ++n_kept;
-                    tiles0 |= pick(cur.tx, sidx) & 0xFFFFu;
-                    tiles1 |= (in_hi ? pick(cur.th, b & 3) : pick(cur.tl, b & 3)) >> 16;
-                }
-            }
-            n_cached = n_kept < KCACHE ? n_kept : KCACHE;
-        } else {
-            // long references: two passes, the winning tiles looked up in the per-tile maxima
-            auto for_each_split = [&](auto&& fn) {
-                for (int gq = 0; 4 * gq <= lq; ++gq) {
-                    const int b_hi = lq - 4 * gq, b_lo = b_hi - 3;
-                    const uint4 x1 = rm4[(int64_t)gq * WAVE];
-                    const uint4 y_hi = rm4[(int64_t)(b_hi >> 2) * WAVE];
-                    const uint4 y_lo = rm4[(int64_t)((b_lo > 0 ? b_lo : 0) >> 2) * WAVE];
-#pragma unroll
-                    for (int sidx = 0; sidx < 4; ++sidx) {
-                        const int a = 4 * gq + sidx, b = lq - a;
-                        if (b >= 0) {
-                            const uint32_t yw = (b >> 2) == (b_hi >> 2) ? pick(y_hi, b & 3) : pick(y_lo, b & 3);
-                            fn(a, b, accept(pick(x1, sidx), 0, nc0, a), accept(yw, 1, nc1, b));
-                        }
-                    }
-                }
-            };
-            for_each_split([&](int, int, int m1, int m2) {
+            for (int sidx = 0; sidx < 4; ++sidx) {
+                const int a = 4 * gq + sidx, b = lq - a;
+                if (b < 0) continue;
+                const bool in_hi = (b >> 2) == (b_hi >> 2);
+                const uint32_t yw = in_hi ? pick(cur.yh, b & 3) : pick(cur.yl, b & 3);
+                const int m1 = accept(pick(cur.x, sidx), 0, nc0, a), m2 = accept(yw, 1, nc1, b);
                 const int sc = m1 + m2;
-                if (sc >= min_score && sc > max_score) max_score = sc;
-            });
-            if (max_score != 0) {
-                first_a = lq;
-                for_each_split([&](int a, int b, int m1, int m2) {
-                    if (m1 + m2 != max_score || m1 == 0 || m2 == 0) return;   // an empty side emits nothing
-                    if (n_kept == 0) first_a = a;
-                    last_a = a;
-                    ++n_kept;
-                    if (small) {
-                        auto tile_max = [&](int c, int row) -> uint32_t {      // rows past the tile's stop are dead (V = 0)
-                            return (row >> 2) < load_tstop(fb.tstop + w * g.nch + c) ? cmax[(w * g.nch + c) * g.lq1 * WAVE + rowidx(row, lane)] : BIAS2;
-                        };
-                        for (int c = 0; c < nc0; ++c)
-                            if (half_of(tile_max(c, a), 0) == m1 + 2 * a) tiles0 |= 1ull << c;
-                        for (int c = 0; c < nc1; ++c)
-                            if (half_of(tile_max(c, b), 1) == m2 + 2 * b) tiles1 |= 1ull << c;
-                    }
-                });
+                if (sc < min_score || sc < max_score) continue;
+                if (sc > max_score) {        // a better split: forget the kept rows so far
+                    max_score = sc;
+                    n_kept = 0;
+                }
+                if (m1 == 0 || m2 == 0) continue;   // an empty side emits nothing
+                if (n_kept == 0) first_a = a;
+                last_a = a;
+                KeptRow kr;
+                kr.a = (int16_t)a;
+                kr.m1 = (int16_t)m1;
+                kr.m2 = (int16_t)m2;
+                kr.pad_ = 0;
+#pragma unroll
+                for (int k = 0; k < KCACHE; ++k)
+                    if (n_kept == k) kcr[k] = __builtin_bit_cast(uint64_t, kr);
+                ++n_kept;
             }
         }
-        if (n_kept > 0) {
-            n_t0 = small ? (unsigned)__builtin_popcountll(tiles0) : (unsigned)nc0;
-            n_t1 = small ? (unsigned)__builtin_popcountll(tiles1) : (unsigned)nc1;
+        n_cached = n_kept < KCACHE ? n_kept : KCACHE;
+    }
+    // The kept rows get their space now, so that one walk over them both stores them and finds their winning tiles.
+    const unsigned long long kb = wave_alloc(&fb.ctr->n_kept, (unsigned)n_kept);
+    const bool kept_fit = kb + n_kept <= kept_cap;
+    if (n_kept > 0) {
+        // The tiles of one side that attain a kept row's maximum, looked up in the per-tile maxima, eight tiles' loads
+        // at a time.  A tile past its stop is dead at that row (V = 0) and a kept side's maximum is positive: skipped.
+        const uint32_t* cm = cmax + w * g.nch * g.lq1 * WAVE;
+        const int32_t* ts = fb.tstop + w * g.nch;
+        const int64_t tstride = (int64_t)g.lq1 * WAVE;
+        auto winners = [&](int h, int n_tiles, int row, int target) -> uint64_t {
+            const int rg = row >> 2;
+            const uint32_t* at = cm + rowidx(row, lane);
+            uint64_t set = 0;
+            for (int c0 = 0; c0 < n_tiles; c0 += 8) {
+                int stop[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) stop[k] = c0 == 0 ? stops.v[k] : (c0 + k < n_tiles ? load_tstop(ts + c0 + k) : 0);
+                uint32_t v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = c0 + k < n_tiles && rg < stop[k] ? at[(c0 + k) * tstride] : BIAS2;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (half_of(v[k], h) == target) set |= 1ull << (c0 + k);
+            }
+            return set;
+        };
+        auto visit = [&](int k, const KeptRow& kr) {
+            if (kept_fit) {
+                kept[kb + k] = kr;
+                if (HANDOFF && k < KCACHE) fl->kc[k * WG_LANES + tid] = __builtin_bit_cast(uint64_t, kr);
+            }
+            if (small) {
+                tiles0 |= winners(0, nc0, kr.a, kr.m1 + 2 * kr.a);
+                tiles1 |= winners(1, nc1, lq - kr.a, kr.m2 + 2 * (lq - kr.a));
+            }
+        };
+        // the first kept rows are still in registers, the rest is re-read
+        int k = 0, a_next = first_a;
+        for (; k < n_cached; ++k) {
+            const KeptRow kr = __builtin_bit_cast(KeptRow, k == 0 ? kcr[0] : k == 1 ? kcr[1] : kcr[KCACHE - 1]);
+            visit(k, kr);
+            a_next = kr.a + 1;
         }
+        for (int a = a_next; k < n_kept && a <= last_a; ++a) {
+            const int m1 = rowmax(0, nc0, a), m2 = rowmax(1, nc1, lq - a);
+            if (m1 + m2 != max_score || m1 == 0 || m2 == 0) continue;
+            KeptRow kr;
+            kr.a = (int16_t)a;
+            kr.m1 = (int16_t)m1;
+            kr.m2 = (int16_t)m2;
+            kr.pad_ = 0;
+            visit(k, kr);
+            ++k;
+        }
+        n_t0 = small ? (unsigned)__builtin_popcountll(tiles0) : (unsigned)nc0;
+        n_t1 = small ? (unsigned)__builtin_popcountll(tiles1) : (unsigned)nc1;
     }
     unsigned n_tasks = n_t0 > n_t1 ? n_t0 : n_t1;
     // Which tile pair does the table-driven replay of this workgroup take for each of its fusions?  All reads of a
@@ -816,12 +819,12 @@ __device__ __forceinline__ void combine_wg(
     // Sort key of the replays: a pair meets its kept rows at row a in M1 and at row lq - a in M2, so lanes
     // sorted by min(a, lq - a) share both hit rows with their neighbours (a and lq - a just swap sides).
     const int fold_a = first_a < lq - first_a ? first_a : lq - first_a;
-    const unsigned want[4] = {(unsigned)n_kept, n_tasks, n_tasks * (unsigned)n_kept, n_gen};
-    unsigned long long base[4];
-    wave_alloc4(fb.ctr, want, base);
-    const unsigned long long kb = base[0], tb = base[1], mb = base[2], gb = base[3];
+    const unsigned want[3] = {n_tasks, n_tasks * (unsigned)n_kept, n_gen};
+    unsigned long long base[3];
+    wave_alloc3(fb.ctr, want, base);
+    const unsigned long long tb = base[0], mb = base[1], gb = base[2];
     bool ok = active && n_kept > 0;
-    if (ok && (kb + n_kept > kept_cap || tb + n_tasks > task_cap || mb + (unsigned long long)n_tasks * n_kept > mask_cap ||
+    if (ok && (!kept_fit || tb + n_tasks > task_cap || mb + (unsigned long long)n_tasks * n_kept > mask_cap ||
                gb + n_gen > gtask_cap))
         ok = false;        // overflow: the host sees the cursors, grows the buffers and reruns the slice
     if (HANDOFF) {
@@ -861,26 +864,6 @@ __device__ __forceinline__ void combine_wg(
     if (!ok) {
         fb.rec_count[g.orig ? g.orig[p] : p] = 0;
         return;
-    }
-    // kept rows: the first ones are still in registers, the rest is re-read
-    int k = 0, a_next = first_a;
-    for (; k < n_cached; ++k) {
-        const KeptRow kr = __builtin_bit_cast(KeptRow, k == 0 ? kcr[0] : k == 1 ? kcr[1] : kcr[KCACHE - 1]);
-        kept[kb + k] = kr;
-        if (HANDOFF) fl->kc[k * WG_LANES + tid] = __builtin_bit_cast(uint64_t, kr);
-        a_next = kr.a + 1;
-    }
-    for (int a = a_next; k < n_kept && a <= last_a; ++a) {
-        const int m1 = rowmax(0, nc0, a), m2 = rowmax(1, nc1, lq - a);
-        if (m1 + m2 != max_score || m1 == 0 || m2 == 0) continue;
-        KeptRow kr;
-        kr.a = (int16_t)a;
-        kr.m1 = (int16_t)m1;
-        kr.m2 = (int16_t)m2;
-        kr.pad_ = 0;
-        kept[kb + k] = kr;
-        if (HANDOFF && k < KCACHE) fl->kc[k * WG_LANES + tid] = __builtin_bit_cast(uint64_t, kr);
-        ++k;
     }
     unsigned gi = 0;
     const uint64_t rest0 = f0 >= 0 && small ? tiles0 & ~(1ull << f0) : tiles0, rest1 = f1 >= 0 && small ? tiles1 & ~(1ull << f1) : tiles1;
@@ -1230,61 +1213,42 @@ __device__ __forceinline__ int sweep_tile_generic(const uint32_t (&r)[WT], const
 }
 
 // After the last tile: rmax = max over tiles of cmax (both fields), so the combine step reads one
-// dword per row instead of one per tile; tmask = which tiles attain it (bit c: M1 tile c, bit 16+c:
-// M2 tile c; only meaningful while a reference has at most 16 tiles, the combine step falls back to
-// cmax otherwise).  cmax of this wave is L2-hot.
-__device__ __forceinline__ uint32_t eq_bits(uint32_t v, uint32_t m, int c)
+// dword per row instead of one per tile.  A tile is read only up to its stop: its rows past it stand for
+// V = 0 (BIAS2), the accumulator's initial value, so leaving them out is exact.  cmax of this wave is L2-hot.
+__device__ __forceinline__ void max4(uint4& m, const uint4& v)
 {
-    // bit c if the lo fields are equal, bit 16+c if the hi fields are: min(v ^ m, 1) per field is the
-    // "differs" flag of both fields at once (one packed instruction instead of two compares and selects)
-    uint32_t differs;
-    const uint32_t one2 = 0x00010001u;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(differs) : "v"(v ^ m), "v"(one2));
-    return (differs ^ one2) << c;
+    m.x = max2(m.x, v.x);
+    m.y = max2(m.y, v.y);
+    m.z = max2(m.z, v.z);
+    m.w = max2(m.w, v.w);
 }
-struct TileStops { int v[8]; };    // stored row groups of a wave's first tiles (wave-uniform)
 // WIDE: with the in-register path for 9 to 16 tiles.  It is a template parameter of the fill kernels (the host picks the
 // instantiation by the slice's tile count) because its mere presence in a kernel costs the sweep of the common, narrower
 // shapes 4 % — the compiler's schedule of the sweep loop is sensitive to what else the kernel holds (profiles/r04/ab_rm16.txt).
 template <bool WIDE>
 __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax, uint32_t* __restrict__ rmax,
-                                               uint32_t* __restrict__ tmask, const int32_t* tstop, const TileStops& stops,
+                                               const int32_t* tstop, const TileStops& stops,
                                                const Geom& g, int w, int lane, int nch_wave, int lq)
 {
     const int ngq = (lq >> 2) + 1;
-    const uint4 dead4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);   // what the rows past a tile's stop stand for
+    const uint4 dead4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint4* out = reinterpret_cast<uint4*>(rmax + (int64_t)w * g.lq1 * WAVE) + lane;
-    uint4* tout = reinterpret_cast<uint4*>(tmask + (int64_t)w * g.lq1 * WAVE) + lane;
     const uint4* src = reinterpret_cast<const uint4*>(cmax + (int64_t)w * g.nch * g.lq1 * WAVE) + lane;
     const int64_t cstride = (int64_t)(g.lq1 >> 2) * WAVE;       // uint4 elements between two tiles
     constexpr int NC = 8;
     if (nch_wave <= NC) {
-        // all tiles of a row group in registers: one round of independent loads, then max and masks
+        // the live tiles of a row group in registers: one round of independent loads, then the maximum (the branches
+        // are wave-uniform; a tile past the wave's last has stop 0)
         for (int gq = 0; gq < ngq; ++gq) {
             uint4 v[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c)
-                v[c] = c < nch_wave ? (gq < stops.v[c] ? src[c * cstride + (int64_t)gq * WAVE] : dead4) : make_uint4(0, 0, 0, 0);
-            uint4 m = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
+                if (gq < stops.v[c]) v[c] = src[c * cstride + (int64_t)gq * WAVE];
+            uint4 m = dead4;
 #pragma unroll
             for (int c = 0; c < NC; ++c)
-                if (c < nch_wave) {
-                    m.x = max2(m.x, v[c].x);
-                    m.y = max2(m.y, v[c].y);
-                    m.z = max2(m.z, v[c].z);
-                    m.w = max2(m.w, v[c].w);
-                }
-            uint4 t = make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (c < nch_wave) {
-                    t.x |= eq_bits(v[c].x, m.x, c);
-                    t.y |= eq_bits(v[c].y, m.y, c);
-                    t.z |= eq_bits(v[c].z, m.z, c);
-                    t.w |= eq_bits(v[c].w, m.w, c);
-                }
+                if (gq < stops.v[c]) max4(m, v[c]);
             out[(int64_t)gq * WAVE] = m;
-            tout[(int64_t)gq * WAVE] = t;
         }
         return;
     }
@@ -1299,49 +1263,24 @@ __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax
             uint4 v[NC], u[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                v[c] = gq < stops.v[c] ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
-                u[c] = NC + c < nch_wave ? (gq < stop_hi[c] ? src[(NC + c) * cstride + (int64_t)gq * WAVE] : dead4) : make_uint4(0, 0, 0, 0);
+                if (gq < stops.v[c]) v[c] = src[c * cstride + (int64_t)gq * WAVE];
+                if (gq < stop_hi[c]) u[c] = src[(NC + c) * cstride + (int64_t)gq * WAVE];
             }
-            uint4 m = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
+            uint4 m = dead4;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                m.x = max2(m.x, v[c].x); m.y = max2(m.y, v[c].y); m.z = max2(m.z, v[c].z); m.w = max2(m.w, v[c].w);
-                if (NC + c < nch_wave) { m.x = max2(m.x, u[c].x); m.y = max2(m.y, u[c].y); m.z = max2(m.z, u[c].z); m.w = max2(m.w, u[c].w); }
-            }
-            uint4 t = make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                t.x |= eq_bits(v[c].x, m.x, c); t.y |= eq_bits(v[c].y, m.y, c); t.z |= eq_bits(v[c].z, m.z, c); t.w |= eq_bits(v[c].w, m.w, c);
-                if (NC + c < nch_wave) {
-                    t.x |= eq_bits(u[c].x, m.x, NC + c); t.y |= eq_bits(u[c].y, m.y, NC + c); t.z |= eq_bits(u[c].z, m.z, NC + c); t.w |= eq_bits(u[c].w, m.w, NC + c);
-                }
+                if (gq < stops.v[c]) max4(m, v[c]);
+                if (gq < stop_hi[c]) max4(m, u[c]);
             }
             out[(int64_t)gq * WAVE] = m;
-            tout[(int64_t)gq * WAVE] = t;
         }
         return;
     }
     for (int gq = 0; gq < ngq; ++gq) {
-        uint4 m = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
-        for (int c = 0; c < nch_wave; ++c) {
-            const uint4 v = gq < uniform(load_tstop(tstop + (int64_t)w * g.nch + c)) ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
-            m.x = max2(m.x, v.x);
-            m.y = max2(m.y, v.y);
-            m.z = max2(m.z, v.z);
-            m.w = max2(m.w, v.w);
-        }
+        uint4 m = dead4;
+        for (int c = 0; c < nch_wave; ++c)
+            if (gq < uniform(load_tstop(tstop + (int64_t)w * g.nch + c))) max4(m, src[c * cstride + (int64_t)gq * WAVE]);
         out[(int64_t)gq * WAVE] = m;
-        if (nch_wave <= TMASK_TILES) {
-            uint4 t = make_uint4(0, 0, 0, 0);
-            for (int c = 0; c < nch_wave; ++c) {
-                const uint4 v = gq < uniform(load_tstop(tstop + (int64_t)w * g.nch + c)) ? src[c * cstride + (int64_t)gq * WAVE] : dead4;
-                t.x |= eq_bits(v.x, m.x, c);
-                t.y |= eq_bits(v.y, m.y, c);
-                t.z |= eq_bits(v.z, m.z, c);
-                t.w |= eq_bits(v.w, m.w, c);
-            }
-            tout[(int64_t)gq * WAVE] = t;
-        }
     }
 }
 
@@ -1354,13 +1293,14 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
                                                            uint32_t* __restrict__ rowcodes,
                                                            const int32_t* __restrict__ min_score_tab,
                                                            uint32_t* __restrict__ bnd, uint32_t* __restrict__ cmax,
-                                                           uint32_t* __restrict__ rmax, uint32_t* __restrict__ tmask,
+                                                           uint32_t* __restrict__ rmax,
                                                            FinishBufs fb, Geom g)
 {
     __shared__ FinishLds fl;
     if (wg_tier[blockIdx.x] != TIER_GENERIC) return;     // a table kernel owns this workgroup (uniform)
     if (threadIdx.x == 0) atomicAdd(&fb.ctr->fill_wgs[FILL_WGS_GENERIC], 1u);
     const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WG_WAVES + (threadIdx.x >> 6)));
+    TileStops stops = {};
     if (w < g.n_waves) {                         // whole waves past the end only join the combine barriers
         const int lane = threadIdx.x & 63;
         const int64_t p = min((int64_t)w * WAVE + lane, g.n_pairs - 1);   // tail lanes shadow the last pair
@@ -1385,7 +1325,6 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
         }
         int l_in = wave_max(lq_lane > 0 ? min(slack >> 2, lq_lane) : 0);
         int stop_prev = 0;
-        TileStops stops = {};
 
         for (int c = 0; c < wi.nch_max; ++c) {
             uint32_t r[WT];
@@ -1408,11 +1347,11 @@ __global__ __launch_bounds__(WG_LANES) void k_fill_generic(const dsa_pair* __res
             l_in = wave_max(last_bnd);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // own stores before own re-reads
-        reduce_row_max<false>(cmax, rmax, tmask, fb.tstop, stops, g, w, lane, wi.nch_max, wi.lq_max);
+        reduce_row_max<false>(cmax, rmax, fb.tstop, stops, g, w, lane, wi.nch_max, wi.lq_max);
     }
     WgView wgi = {};                             // no tables, no groups: every task goes to k_replay
     wgi.list = nullptr;
-    combine_wg<false, WT>(pairs, fusions, cmax, rmax, tmask, min_score_tab, wgi, 0, false, &fl, fb, g);
+    combine_wg<false, WT>(pairs, fusions, cmax, rmax, stops, min_score_tab, wgi, 0, false, &fl, fb, g);
 }
 
 // The sweep of one tile by one wave of the table kernels (TIER 0: 25-row tables, SPLIT: two 5-row tables per fusion): rows in
@@ -1611,7 +1550,7 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
                                                            const int32_t* __restrict__ min_score_tab,
                                                            const dsa_fusion* __restrict__ fusions,
                                                            uint32_t* __restrict__ bnd, uint32_t* __restrict__ cmax,
-                                                           uint32_t* __restrict__ rmax, uint32_t* __restrict__ tmask,
+                                                           uint32_t* __restrict__ rmax,
                                                            FinishBufs fb, Geom g)
 {
     constexpr bool SPLIT = TIER > 0;
@@ -1724,12 +1663,12 @@ __global__ __launch_bounds__(WG_LANES, TIER == 2 ? 2 : DSA_FAST_WGS) void k_fill
     if (DIAG_TAIL) {
         if (live) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // own stores before own re-reads
-            reduce_row_max<WIDE>(cmax, rmax, tmask, fb.tstop, stops, g, w, lane, wi.nch_max, wi.lq_max);
+            reduce_row_max<WIDE>(cmax, rmax, fb.tstop, stops, g, w, lane, wi.nch_max, wi.lq_max);
         }
         t_rowmax = clk.lap();
         // The latency-bound finish work of this workgroup runs here, in the shadow of the other resident
         // workgroups' sweeps, instead of in kernels of its own.
-        combine_wg<true, WT>(pairs, fusions, cmax, rmax, tmask, min_score_tab, wgi, my_group, true, &fl, fb, g);
+        combine_wg<true, WT>(pairs, fusions, cmax, rmax, stops, min_score_tab, wgi, my_group, true, &fl, fb, g);
         t_combine = clk.lap();
         if (DIAG_REPLAY) replay_fast_wg<SPLIT, WT>(T, &fl, wgi, fb, refcodes, rowcodes, bnd, g);
         t_replay = clk.lap();

@@ -16,7 +16,7 @@ constexpr int TILE_WIDTHS[] = {64, 60, 56};
 constexpr int N_TILE_WIDTHS = sizeof(TILE_WIDTHS) / sizeof(TILE_WIDTHS[0]);
 
 // Tile counts the kernels treat alike: up to 8 tiles (row-maximum reduction in registers, tile votes of the combine step),
-// up to 16 (the WIDE reduction, winning-tile masks), up to 64 (minimal replay), up to 255 (tile indices are bytes, 255 = none:
+// up to 16 (the WIDE reduction, the 16-bit tile sets of a PairState), up to 64 (minimal replay), up to 255 (tile indices are bytes, 255 = none:
 // the longest window of the 16-bit kernels, 16320 bases, is 255 tiles of 64) and beyond.
 constexpr int tile_count_class(int tiles) { return tiles <= 8 ? 0 : tiles <= 16 ? 1 : tiles <= 64 ? 2 : tiles <= 255 ? 3 : 4; }
 constexpr int tiles_of(int len, int wt) { return (len + wt - 1) / wt; }
