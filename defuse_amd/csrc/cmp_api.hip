@@ -51,7 +51,9 @@ __host__ __device__ inline int rec_end(const cmp_record& a) { return (int)((a.me
 // RefBinPacked as one word (:28-65): the caller has checked ref < 2^18 and bin < 2^13
 __host__ __device__ inline uint32_t pack_ref_bin(int ref, int strand, int bin) { return (uint32_t)ref | ((uint32_t)strand << 18) | (((uint32_t)bin & 0x1FFFu) << 19); }
 
-// the first (alignment, bin) of a fragment on which AddBinPairs would stop, in its loop order (:252-266); 0 = none
+// the first (alignment, bin) of a fragment on which AddBinPairs would stop, in its loop order (:252-266); 0 = none.  For one
+// (alignment, bin) the reference builds the RefBinPacked first (:258 — too many reference sequences, then chromosome too
+// large, :33-47) and packs the alignment after it (:260 — the four relative-position checks of :183-186).
 __host__ __device__ inline int fragment_error(const cmp_record* r, int n, int mfr, int& bad, int& value)
 {
     for (int i = 0; i < n; ++i) {
@@ -59,9 +61,9 @@ __host__ __device__ inline int fragment_error(const cmp_record* r, int n, int mf
         for (int b = sb; b <= eb; ++b) {
             const int rs = r[i].start - b * BIN_LENGTH + BIN_LENGTH / 2, re = r[i].end - b * BIN_LENGTH + BIN_LENGTH / 2;
             bad = i;
-            if (rs < 0 || re < 0 || rs >= (1 << 16) || re >= (1 << 16)) return 1;
             if (rec_ref(r[i]) >= (1 << 18)) { value = rec_ref(r[i]); return 2; }
             if (b >= (1 << 13)) { value = b; return 3; }
+            if (rs < 0 || re < 0 || rs >= (1 << 16) || re >= (1 << 16)) return 1;
         }
     }
     return 0;

@@ -1,5 +1,5 @@
 // sc_api.hip — greedy set cover on gfx950 (include/defuse_sc.h), replacing SetCover() of
-// tools/setcover.cpp:30-110.  Integer/byte work: radix sort + label propagation are HBM-bound, the
+// tools/setcover.cpp:30-110.  Integer/byte work: radix sort + component labelling are HBM-bound, the
 // per-component greedy is latency-bound; nothing here is shaped into a GEMM.
 #include <hip/hip_runtime.h>
 
@@ -48,36 +48,48 @@ __global__ void k_iota(int32_t* __restrict__ a, int32_t n)
     if (i < n) a[i] = i;
 }
 
-// hook: every fragment pulls the labels of its clusters down to their minimum
+// root of c's tree.  label[x] <= x always (a hook only ever lowers a label), so the walk ends
+__device__ __forceinline__ int root_of(const int32_t* label, int c)
+{
+    int r = c, p;
+    while ((p = label[r]) != r) r = p;
+    return r;
+}
+
+// hook: every fragment hangs the ROOTS of its clusters' trees under the smallest of them.  Lowering the label of the cluster
+// itself would let a label advance one cluster per round along a chain of clusters; a root moves its whole tree.  In two
+// rounds a tree either hangs under another or has taken in every tree it touched, so the trees of a component halve every
+// two rounds and the number of rounds is logarithmic in the clusters, whatever the shape of the component.
 __global__ void k_hook(const int64_t* __restrict__ e2c_off, const int32_t* __restrict__ e2c, int32_t max_element,
-                       int32_t* __restrict__ label, int* __restrict__ changed)
+                       int32_t* label, int* __restrict__ changed)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e > max_element) return;
     const int64_t b = e2c_off[e], en = e2c_off[e + 1];
     if (en - b < 2) return;
     int m = 0x7FFFFFFF;
-    for (int64_t k = b; k < en; ++k) m = min(m, label[e2c[k]]);
+    for (int64_t k = b; k < en; ++k) m = min(m, root_of(label, e2c[k]));
     for (int64_t k = b; k < en; ++k) {
-        const int c = e2c[k];
-        if (label[c] > m) {
-            atomicMin(&label[c], m);
+        const int r = root_of(label, e2c[k]);
+        if (r > m) {                            // m < r and in r's component: the forest stays a forest
+            atomicMin(&label[r], m);
             *changed = 1;
         }
     }
 }
 
-// compress: label[c] = label[label[c]] until it is a root
-__global__ void k_compress(int32_t* __restrict__ label, int32_t n, int* __restrict__ changed)
+// compress: every cluster jumps to its grandparent until its parent is a root.  No hook runs beside this kernel, so the
+// roots stand still and a lane writes its own label only; the jumps of the others shorten its way.
+__global__ void k_compress(int32_t* label, int32_t n)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n) return;
-    int l = label[c];
-    int r = l;
-    while (label[r] != r) r = label[r];
-    if (r != l) {
-        label[c] = r;
-        *changed = 1;
+    int p = label[c];
+    for (;;) {
+        const int g = label[p];
+        if (g == p) break;
+        label[c] = g;
+        p = g;
     }
 }
 
@@ -258,14 +270,14 @@ extern "C" int sc_cover(int device, const int64_t* cluster_off, const int32_t* e
     hipLaunchKernelGGL(k_lower_bounds, grid(nel + 1), dim3(B), 0, 0, d_keys_sorted.p, n_occ, max_element, d_e2c_off.p);
     SC_HIP(hipEventRecord(ev[1]));
 
-    // 2. connected components of the cluster/fragment graph
+    // 2. connected components of the cluster/fragment graph: root hooking + full compression until a round hooks nothing
     hipLaunchKernelGGL(k_iota, grid(n_clusters), dim3(B), 0, 0, d_label.p, n_clusters);
     int iterations = 0;
     for (;;) {
         int changed = 0;
         SC_HIP(hipMemset(d_changed.p, 0, sizeof(int)));
         hipLaunchKernelGGL(k_hook, grid(nel), dim3(B), 0, 0, d_e2c_off.p, d_e2c.p, max_element, d_label.p, d_changed.p);
-        hipLaunchKernelGGL(k_compress, grid(n_clusters), dim3(B), 0, 0, d_label.p, n_clusters, d_changed.p);
+        hipLaunchKernelGGL(k_compress, grid(n_clusters), dim3(B), 0, 0, d_label.p, n_clusters);
         SC_HIP(hipMemcpy(&changed, d_changed.p, sizeof(int), hipMemcpyDeviceToHost));
         ++iterations;
         if (!changed) break;

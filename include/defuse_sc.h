@@ -22,7 +22,7 @@ extern "C" {
 
 typedef struct sc_timing {
     float   build_ms;        /* fragment -> clusters index (radix sort) */
-    float   components_ms;   /* connected components (label propagation) */
+    float   components_ms;   /* connected components (root hooking)    */
     float   greedy_ms;       /* per-component greedy */
     float   total_ms;
     int32_t n_components;

@@ -66,8 +66,40 @@ def read_exons(path):
 
 
 def _fmt(x):
-    s = "%g" % x
-    return s
+    # The only NaN this tool makes is 0.0/0.0 (CalculateSplitPos / CalculateSplitMin on an anchored range of 0 or 1 bases).
+    # x86: a run-time 0.0/0.0 is the default NaN with the sign bit set, and the reference's stream prints it as "-nan"
+    # (the same rule as oracle/localalign_oracle.py and tests/matealign_oracle.py; reasoned, not run: see the parity status).
+    if x != x:
+        return "-nan"
+    return "%g" % x
+
+
+def sample_batch(sample_off, sample_pos, fragments, trim, anchor):
+    """The per-fragment sampling (tools/calccov.cpp:155-215) of fragments (ref, (start0, end0), (start1, end1)) in order:
+    returns (length_idx, length_val, split_idx, split_pos, split_min) as lists, a fragment's length samples by sample
+    index, its split samples read 0 then read 1, each by sample index."""
+    length_idx, length_val, split_idx, split_pos, split_min = [], [], [], [], []
+    for (r, (s0, e0), (s1, e1)) in fragments:
+        us, ue = min(s0 + trim, s1 + trim), max(e0 - trim, e1 - trim)
+        flen = max(e0, e1) - min(s0, s1)
+        idx = range(sample_off[r], sample_off[r + 1])
+        for k in idx:
+            if us <= sample_pos[k] <= ue:
+                length_idx.append(k)
+                length_val.append(flen)
+        for (s, e) in ((s0, e0), (s1, e1)):
+            a_s, a_e = s + anchor, e - anchor + 1
+            for k in idx:
+                p = sample_pos[k]
+                if a_s <= p <= a_e:
+                    pos_value = max(0.0, float(p - s - anchor))
+                    pos_range = e - s + 1.0 - 2.0 * anchor
+                    min_value = max(0.0, float(min(p - s - anchor, e + 1 - p - anchor)))
+                    min_range = math.floor(0.5 * (e - s + 1.0 - 2.0 * anchor))
+                    split_idx.append(k)
+                    split_pos.append(_div(pos_value, pos_range))
+                    split_min.append(_div(min_value, float(min_range)))
+    return length_idx, length_val, split_idx, split_pos, split_min
 
 
 def calccov(conc_sam, genetran, density, anchor, trim, multiexon=False):
@@ -84,32 +116,14 @@ def calccov(conc_sam, genetran, density, anchor, trim, multiexon=False):
             for _ in range(n):
                 sample_pos.append(rng.rand() % length[tr[0]] + 1)
             sample_off.append(len(sample_pos))
-    out_len, out_pos, out_min = [], [], []
+    fragments = []
 
     def fragment(alns):
         if len(alns) != 2:
             raise SystemExit("Error: expected 2 alignments per fragment\nretrieved %d alignments for %s" % (len(alns), alns[0][0]))
         if alns[0][2] not in ref_index:
             return
-        r = ref_index[alns[0][2]]
-        (s0, e0), (s1, e1) = (alns[0][4], alns[0][5]), (alns[1][4], alns[1][5])
-        us, ue = min(s0 + trim, s1 + trim), max(e0 - trim, e1 - trim)
-        flen = max(e0, e1) - min(s0, s1)
-        idx = range(sample_off[r], sample_off[r + 1])
-        for k in idx:
-            if us <= sample_pos[k] <= ue:
-                out_len.append("%d\t%d\n" % (k, flen))
-        for (s, e) in ((s0, e0), (s1, e1)):
-            a_s, a_e = s + anchor, e - anchor + 1
-            for k in idx:
-                p = sample_pos[k]
-                if a_s <= p <= a_e:
-                    pos_value = max(0.0, float(p - s - anchor))
-                    pos_range = e - s + 1.0 - 2.0 * anchor
-                    min_value = max(0.0, float(min(p - s - anchor, e + 1 - p - anchor)))
-                    min_range = math.floor(0.5 * (e - s + 1.0 - 2.0 * anchor))
-                    out_pos.append("%d\t%s\n" % (k, _fmt(_div(pos_value, pos_range))))
-                    out_min.append("%d\t%s\n" % (k, _fmt(_div(min_value, min_range))))
+        fragments.append((ref_index[alns[0][2]], (alns[0][4], alns[0][5]), (alns[1][4], alns[1][5])))
     cur = []
     for rec in ora.sam_alignments(conc_sam):
         if cur and rec[0] != cur[0][0]:
@@ -118,7 +132,9 @@ def calccov(conc_sam, genetran, density, anchor, trim, multiexon=False):
         cur.append(rec)
     if cur:
         fragment(cur)
-    return "".join(out_len), "".join(out_pos), "".join(out_min)
+    li, lv, si, sp, sm = sample_batch(sample_off, sample_pos, fragments, trim, anchor)
+    return ("".join("%d\t%d\n" % kv for kv in zip(li, lv)), "".join("%d\t%s\n" % (k, _fmt(v)) for k, v in zip(si, sp)),
+            "".join("%d\t%s\n" % (k, _fmt(v)) for k, v in zip(si, sm)))
 
 
 def _div(a, b):      # IEEE division: x/0 is +-inf or nan, not an exception

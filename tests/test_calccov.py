@@ -114,3 +114,174 @@ def test_tool_matches_oracle(tools, tmp_path, multiexon, threads):
     assert r.returncode == 0, r.stderr
     assert (open(out + ".len").read(), open(out + ".pos").read(), open(out + ".min").read()) == exp
     assert len(exp[0].splitlines()) > 200
+
+
+# ---- the NaN lines: an anchored range of 0 or 1 bases ---------------------------------------------------------------------
+
+def test_oracle_prints_every_nan_as_the_reference_does():
+    from oracle import calccov_oracle as c
+    nan = float("nan")
+    assert c._fmt(nan) == "-nan" and c._fmt(-nan) == "-nan" and c._fmt(c._div(0.0, 0.0)) == "-nan"
+    assert c._fmt(0.5) == "0.5" and c._fmt(0.0) == "0" and c._fmt(1.0) == "1"
+
+
+@pytest.mark.parametrize("rl", [50, 51])
+def test_oracle_nan_lines(tmp_path, rl):
+    """Reads of 2 x anchor bases have an anchored range of 0 (one position, 0/0 in both files), reads of 2 x anchor + 1 a
+    range of 1 (two positions, 0/1 and 1/1 in the split positions, 0/floor(0.5) in the split minimums)."""
+    from oracle import calccov_oracle as c
+    sam, regions = make_case(str(tmp_path), seed=5, n_genes=12, n_frag=1500, rl=rl)
+    ln, pos, mn = c.calccov(sam, regions, 0.05, 25, 50)
+    assert len(mn.splitlines()) == len(pos.splitlines()) > 20 and "nan" not in ln
+    assert all(l.endswith("\t-nan") for l in mn.splitlines())
+    if rl == 50:
+        assert all(l.endswith("\t-nan") for l in pos.splitlines())
+    else:
+        assert {l.split("\t")[1] for l in pos.splitlines()} == {"0", "1"}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rl", [50, 51])
+def test_tool_nan_lines(tools, tmp_path, rl):
+    """The same two inputs through the tool: the NaN lines are "-nan" whatever sign the device's division left, the length
+    samples are untouched by it."""
+    from oracle import calccov_oracle as c
+    sam, regions = make_case(str(tmp_path), seed=5, n_genes=12, n_frag=1500, rl=rl)
+    exp = c.calccov(sam, regions, 0.05, 25, 50)
+    out = str(tmp_path / "cov")
+    r = run_tool(sam, regions, out, density="0.05", anchor="25")
+    assert r.returncode == 0, r.stderr
+    got = (open(out + ".len").read(), open(out + ".pos").read(), open(out + ".min").read())
+    assert got == exp
+    assert "\t-nan\n" in got[2] and ("\t-nan\n" in got[1]) == (rl == 50) and len(got[0].splitlines()) > 20 and "nan" not in got[0]
+
+
+# ---- the kernel itself (include/defuse_cov.h through defuse_amd/cov.py) against the oracle's sample_batch -----------------
+
+RANGES = (-1, 0, 1, 2, 3, 46)                  # end - start + 1 - 2 x anchor: empty below 0, 0/0 at 0, x/floor(0.5) at 1
+ANCHORS = (0, 4, 25)
+TRIMS = (0, 50, 1000)                          # 1000: unseqStart > unseqEnd, no length sample at all
+COUNTS = (1, 255, 256, 257, 513)               # around one block of 256 lanes, and more than two
+
+
+def cov_samples():
+    """Three transcripts: 0 without a sample, 1 with one (position 30), 2 of 120 bases with every position sampled, in no
+    order, and four positions twice."""
+    rng = np.random.default_rng(8)
+    pos2 = list(range(1, 121)) + [10, 10 + 47, 57, 120]
+    rng.shuffle(pos2)
+    pos = [30] + pos2
+    return [0, 0, 1, len(pos)], pos
+
+
+def cov_fragments(n, anchor):
+    """n fragments whose two reads run through RANGES independently of each other; on transcript 2 mostly, every 7th on
+    transcript 1 and every 11th on transcript 0; the second read equal to the first, in front of it, behind it, or apart.
+    Fragment 0 spans transcript 2."""
+    frs = []
+    for i in range(n):
+        l0, l1 = RANGES[i % 6] + 2 * anchor, RANGES[(i // 6) % 6] + 2 * anchor
+        ref = 0 if i % 11 == 10 else 1 if i % 7 == 6 else 2
+        s0 = 1 + (7 * i) % 113
+        how = (i // 3) % 4
+        if how == 0:
+            s1, l1 = s0, l0                                             # both ends identical
+        elif how == 1:
+            s1 = max(1, s0 - 3 - i % 40)                                 # end 1 in front of end 0
+        elif how == 2:
+            s1 = s0 + 5 + i % 60
+        else:
+            s1 = 1 + (13 * i) % 119
+        frs.append((ref, (s0, s0 + l0 - 1), (s1, s1 + l1 - 1)))
+    frs[0] = (2, (3, 3 + RANGES[0] + 2 * anchor - 1), (100, 118))
+    return frs
+
+
+def bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def cov_expected():
+    """The oracle's arrays for every (anchor, trim, count), computed once; with what the inputs are meant to reach."""
+    from oracle import calccov_oracle as c
+    off, pos = cov_samples()
+    exp = {}
+    for anchor in ANCHORS:
+        for trim in TRIMS:
+            for n in COUNTS:
+                exp[(anchor, trim, n)] = c.sample_batch(off, pos, cov_fragments(n, anchor), trim, anchor)
+    for anchor in ANCHORS:
+        li, lv, si, sp, sm = exp[(anchor, 0, 513)]
+        sp, sm = np.array(sp), np.array(sm)
+        assert np.isnan(sp).any()                                                    # range 0
+        assert (np.isnan(sm) & np.isfinite(sp)).any()                                # range 1
+        assert np.isfinite(sm).any() and (sp[np.isfinite(sp)] <= 1.0).all()
+        per = [c.sample_batch(off, pos, [f], 0, anchor) for f in cov_fragments(513, anchor)]
+        assert sum(1 for p in per if not p[0] and not p[2]) > 10                     # fragments with no output
+        assert len(per[0][0]) > 100                                                  # one fragment with more than 100 samples
+        assert sum(len(p[0]) for p in per) == len(li) and sum(len(p[2]) for p in per) == len(si)
+        assert not exp[(anchor, 1000, 513)][0] and exp[(anchor, 1000, 513)][2] == si  # the trim only moves the length samples
+    return exp
+
+
+def test_cov_inputs_reach_the_edges(cov_expected):
+    assert len(cov_expected) == 45
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("anchor", ANCHORS)
+def test_gpu_sample_batch_equals_the_oracle(built, cov_expected, anchor):
+    """Indices and lengths exactly; doubles bit for bit where finite (IEEE division and floor are the same values on both
+    sides); a NaN only as a NaN, its sign is the tool's to print."""
+    from defuse_amd import cov
+    off, pos = cov_samples()
+    signs = set()
+    for trim in TRIMS:
+        for n in COUNTS:
+            li, lv, si, sp, sm = cov_expected[(anchor, trim, n)]
+            g_li, g_lv, g_si, g_sp, g_sm, t = cov.sample_batch(off, pos, cov.fragments_array(cov_fragments(n, anchor)), trim, anchor)
+            assert g_li.tolist() == li and g_lv.tolist() == lv and g_si.tolist() == si, (anchor, trim, n)
+            assert (t.n_length_samples, t.n_split_samples) == (len(li), len(si))
+            for got, want in ((g_sp, np.array(sp, dtype=np.float64)), (g_sm, np.array(sm, dtype=np.float64))):
+                assert (np.isnan(got) == np.isnan(want)).all(), (anchor, trim, n)
+                fin = ~np.isnan(want)
+                assert (bits(got)[fin] == bits(want)[fin]).all(), (anchor, trim, n)
+                signs |= set(np.signbit(got[np.isnan(got)]).tolist())
+    print("sign bit of the device's 0.0/0.0:", sorted(signs))
+
+
+def test_sample_batch_refuses_bad_arguments_before_it_needs_a_device(built):
+    from defuse_amd import cov, dsa
+    off, pos = cov_samples()
+
+    def call(off, frs):
+        room = (np.full(4, -7, np.int32), np.full(4, -7, np.int32), np.full(4, -7, np.int32), np.full(4, 7.5), np.full(4, 7.5))
+        rc, nl, ns, _ = cov.sample_batch_raw(off, pos, cov.fragments_array(frs), 0, 4, *room)
+        assert all((a == a[0]).all() for a in room)
+        return rc, nl, ns
+    assert call(off, []) == (0, 0, 0)                                                # no fragment: DSA_OK, nothing needed
+    good = cov_fragments(5, 4)
+    for bad_ref in (-1, 3):
+        assert call(off, good + [(bad_ref, (1, 50), (60, 110))])[0] == dsa.DSA_E_ARG
+    assert call([0, 1, 0, len(pos)], good)[0] == dsa.DSA_E_ARG                       # ref_sample_off descends
+
+
+@pytest.mark.gpu
+def test_gpu_sample_batch_capacity_protocol(built, cov_expected):
+    """A capacity one short on either side: DSA_E_CAPACITY, both needed counts, nothing written."""
+    from defuse_amd import cov, dsa
+    off, pos = cov_samples()
+    li, lv, si, sp, sm = cov_expected[(4, 0, 257)]
+    frs = cov.fragments_array(cov_fragments(257, 4))
+    for short_len, short_split in ((1, 0), (0, 1), (1, 1)):
+        nl, ns = len(li) - short_len, len(si) - short_split
+        room = (np.full(nl, -7, np.int32), np.full(nl, -7, np.int32), np.full(ns, -7, np.int32), np.full(ns, 7.5), np.full(ns, 7.5))
+        rc, need_l, need_s, _ = cov.sample_batch_raw(off, pos, frs, 0, 4, *room)
+        assert (rc, need_l, need_s) == (dsa.DSA_E_CAPACITY, len(li), len(si))
+        assert all((a == (7.5 if a.dtype == np.float64 else -7)).all() for a in room)
+    room = (np.zeros(len(li), np.int32), np.zeros(len(li), np.int32), np.zeros(len(si), np.int32), np.zeros(len(si)), np.zeros(len(si)))
+    rc, need_l, need_s, _ = cov.sample_batch_raw(off, pos, frs, 0, 4, *room)            # exactly enough
+    assert (rc, need_l, need_s) == (0, len(li), len(si)) and room[0].tolist() == li and room[2].tolist() == si
+    rc, need_l, need_s, _ = cov.sample_batch_raw(off, pos, frs[:0], 0, 4, *room)        # no fragment
+    assert (rc, need_l, need_s) == (0, 0, 0)

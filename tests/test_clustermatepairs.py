@@ -204,18 +204,41 @@ def test_device_bin_pairs_through_the_c_abi(built):
         assert lib.cmp_bin_run(h, mfr, ctypes.byref(st)) == 0, lib.cmp_last_error()
         return st, starts
 
-    for seed, mfr in ((1, 600), (5, 1500), (7, 250)):
-        frs = tb.random_fragments(seed, 3000)
-        st, _ = run(frs, mfr)
-        exp, conc = tb.oracle_bin_pairs(frs, mfr)
-        assert st.err_record == -1 and st.n_concordant == conc and st.n_keys == len(exp)
+    def fetch(st):
         keys = np.zeros(st.n_keys, dtype=np.uint64)
         off1, off2 = np.zeros(st.n_keys + 1, dtype=np.int64), np.zeros(st.n_keys + 1, dtype=np.int64)
         p1, p2 = np.zeros(st.n_first, dtype=tb.PACKED), np.zeros(st.n_second, dtype=tb.PACKED)
         assert lib.cmp_bin_fetch(h, keys.ctypes.data, off1.ctypes.data, off2.ctypes.data, p1.ctypes.data, p2.ctypes.data) == 0
         assert list(keys) == sorted(keys) and len(set(keys.tolist())) == len(keys)
-        got = tb.as_lists(keys, off1, off2, p1.tolist(), p2.tolist())
-        assert got == {k: (v[0], v[1]) for k, v in exp.items()}
+        return tb.as_lists(keys, off1, off2, p1.tolist(), p2.tolist())
+
+    import time
+    t0 = time.perf_counter()
+    for seed, mfr in ((1, 600), (5, 1500), (7, 250)):
+        frs = tb.random_fragments(seed, 3000)
+        st, _ = run(frs, mfr)
+        exp, conc = tb.oracle_bin_pairs(frs, mfr)
+        assert st.err_record == -1 and st.n_concordant == conc and st.n_keys == len(exp)
+        assert fetch(st) == {k: (v[0], v[1]) for k, v in exp.items()}
+    # ends of 256 entries and more (tests/test_cmp_bins.py:heavy_fragments): Distinct::first beyond its bitmap
+    t1 = time.perf_counter()
+    heavy = [tb.heavy_fragments(20 + k, n0, n1) for k, (n0, n1) in enumerate(tb.HEAVY_CASES)]
+    lengths, late_first, seen_again = tb.heavy_coverage(heavy)
+    assert {256, 257} <= lengths and late_first and seen_again
+    for frs in heavy:
+        st, _ = run(frs, tb.HEAVY_MFR)
+        exp, conc = tb.oracle_bin_pairs(frs, tb.HEAVY_MFR)
+        assert st.err_record == -1 and conc == 0 and st.n_concordant == 0 and st.n_keys == len(exp)
+        assert fetch(st) == {k: (v[0], v[1]) for k, v in exp.items()}
+        print("heavy ends: %d keys, device %.1f ms" % (st.n_keys, st.device_ms))
+    t2 = time.perf_counter()
+    # the stop conditions of one (alignment, bin) in the reference's order, with a minFusionRange above half a bin
+    for offender in sorted(tb.STOP_OFFENDERS):
+        frs, record = tb.stop_fragments(offender)
+        st, _ = run(frs, tb.STOP_MFR)
+        assert tb.oracle_stop_kind(frs, tb.STOP_MFR) == (5, tb.STOP_OFFENDERS[offender][2])
+        assert (st.err_kind, st.err_record) == (tb.STOP_OFFENDERS[offender][2], record), offender
+    print("random fragments %.1f s, heavy ends %.1f s, stop order %.1f s" % (t1 - t0, t2 - t1, time.perf_counter() - t2))
     frs = tb.random_fragments(9, 50)
     frs[20][0]["ref"] = (1 << 18) + 5
     frs[30][0]["region"] = ((1 << 13) * 32768 + 10, (1 << 13) * 32768 + 80)
@@ -236,6 +259,74 @@ def test_device_bin_pairs_through_the_c_abi(built):
     st = Stats()
     assert lib.cmp_bin_run(h, 600, ctypes.byref(st)) == 0 and st.n_keys == 0
     lib.cmp_bin_destroy(h)
+
+
+def stop_input(offender):
+    """tests/test_cmp_bins.py:stop_fragments as the tool's input, -u 10000 -s 1000 (minFusionRange 20000).  Reference indices
+    are given in order of appearance, so for the offender on a reference >= 2^18 that many references come first: fragments
+    of two alignments on references of their own, after the five fragments in front of the offender.  Returns (lines, the
+    lines the reference writes to stdout before it stops, its message on stderr up to where the file name begins)."""
+    from oracle import clustermatepairs_oracle as ora
+    from tests import test_cmp_bins as tb
+    frs, _ = tb.stop_fragments(offender)
+    _, _, kind, message = tb.STOP_OFFENDERS[offender]
+    text = lambda a, name: "%d\t%d\t%s\t%s\t%d\t%d\n" % (a["frag"], a["readEnd"], name, "+-"[a["strand"]], a["region"][0], a["region"][1])
+    lines = [text(a, "r%d" % a["ref"]) for als in frs[:5] for a in als]
+    n_refs = 2
+    if kind == 2:
+        for f in range((1 << 17) - 1):                                    # with r0 and r1: indices 0 .. 2^18 - 1
+            start = (2 + f % 50) * 32768 + 21000 + f % 8000
+            lines.append("%d\t0\tp%da\t+\t%d\t%d\n" % (2000 + f, f, start, start + 49))
+            lines.append("%d\t1\tp%db\t-\t%d\t%d\n" % (2000 + f, f, start + 500, start + 549))
+        n_refs += 2 * ((1 << 17) - 1)
+    lines += [text(a, "r%d" % a["ref"]) for als in frs[5:] for a in als]
+    # the oracle on the same fragments, the offender's reference at the index the tool will give it
+    if kind == 2:
+        frs[5][1]["ref"] = n_refs
+    with pytest.raises(SystemExit) as stop:
+        for als in frs:
+            ora.add_fragment(als, 20000, {})
+    if kind != 1:
+        assert str(stop.value) == message
+    else:
+        assert str(stop.value) == "Error: relativeStart out of range"          # the oracle does not tell the four checks apart
+    numbers = {1: "", 2: "%d\n%d\n" % (n_refs, 1 << 18), 3: "%d\n%d\n" % (1 << 13, 1 << 13)}[kind]
+    return lines, numbers, message
+
+
+def run_stop_tool(offender, tmp_path, env):
+    lines, numbers, message = stop_input(offender)
+    p = tmp_path / "spanning.txt"
+    p.write_text("".join(lines))
+    r = subprocess.run([TOOL, "-a", str(p), "-c", str(tmp_path / "clusters.txt"), "-u", "10000", "-s", "1000", "-p", "0.95", "-m", "5"],
+                       capture_output=True, text=True, env=dict(os.environ, **env))
+    assert r.returncode == 1
+    assert r.stdout == "Finding pairs of reference sequences connected by pairs of alignments\n" + numbers
+    # the reference ends a DebugCheck's message with its build's __FILE__, which is not known here: compared up to " of "
+    assert r.stderr.startswith(message) and r.stderr.count("\n") == 1, r.stderr
+    if not message.endswith(" of "):
+        assert r.stderr == message + "\n"
+
+
+STOP_OFFENDERS = ["bin", "end_high", "reference", "start_high", "start_low"]
+
+
+@pytest.mark.parametrize("offender", STOP_OFFENDERS)
+def test_host_binning_stops_where_the_reference_stops(built, tmp_path, offender):
+    """No GPU needed.  For one (alignment, bin) the reference builds the RefBinPacked (too many reference sequences, then
+    chromosome too large, tools/clustermatepairs.cpp:33-47, :258) before it packs the alignment (the four relative-position
+    checks, :183-186, :260); the host transcription stops on the same one with the same words."""
+    from defuse_amd import build
+    build.build_tools()
+    run_stop_tool(offender, tmp_path, {"DEFUSE_CMP_HOST_BINNING": "1", "DEFUSE_THREADS": "3"})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("offender", STOP_OFFENDERS)
+def test_device_binning_stops_where_the_reference_stops(built, tmp_path, offender):
+    from defuse_amd import build
+    build.build_tools()
+    run_stop_tool(offender, tmp_path, {})
 
 
 @pytest.mark.gpu

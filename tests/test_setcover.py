@@ -184,3 +184,269 @@ def test_setcover_tool_cluster_lines_in_any_order(built, tmp_path, threads):
     assert r.returncode == 0, r.stderr
     exp = o.setcover(str(p), 3)
     assert outp.read_text() == exp and len(exp.splitlines()) > 100
+
+
+# ---- connected components: a label that has to travel the length of a chain ------------------------------------------------
+
+def label_chain(n, ids, first_element=0):
+    """One component of n clusters, the path 0 - (n-1) - (n-2) - ... - 1 (cluster indices), consecutive clusters of the path
+    sharing one element; the shared elements' ids descend ("down") or ascend ("up") along the path from cluster 0.  Every
+    cluster also holds one element of its own, so the greedy has sizes that tie.  Elements are first_element .. first_element
+    + 2n - 2."""
+    assert n >= 2 and ids in ("down", "up")
+    path = [0] + list(range(n - 1, 0, -1))
+    clusters = [[] for _ in range(n)]
+    for j in range(n - 1):
+        e = first_element + (j if ids == "up" else n - 2 - j)
+        clusters[path[j]].append(e)
+        clusters[path[j + 1]].append(e)
+    for c in range(n):
+        clusters[c].append(first_element + n - 1 + c)
+    return clusters
+
+
+def element_lists(clusters):
+    e2c = {}
+    for c, lst in enumerate(clusters):
+        for e in lst:
+            e2c.setdefault(e, []).append(c)
+    return [e2c[e] for e in sorted(e2c)]                                 # ascending element id = ascending lane
+
+
+def rounds_cluster_hooking(clusters, schedule, cap):
+    """The component rounds as they were before hooking went to the roots, in plain Python.  Hook: every element lowers the
+    label of each of ITS CLUSTERS to the minimum label among them.  Compress: label[c] = root of label[c].  One round = one
+    launch of each and one look at the `changed` flag.  schedule "lockstep": a launch reads all labels before it writes any
+    (64 consecutive elements are one wave; nothing cascades inside a launch); "serial": elements one after the other in
+    ascending id, each seeing what the earlier ones wrote."""
+    label = list(range(len(clusters)))
+    lists = [l for l in element_lists(clusters) if len(l) >= 2]
+    for rounds in range(1, cap + 1):
+        changed = False
+        src = list(label) if schedule == "lockstep" else label
+        for l in lists:
+            m = min(src[c] for c in l)
+            for c in l:
+                if src[c] > m:
+                    label[c] = min(label[c], m)
+                    changed = True
+        for c in range(len(label)):
+            r = label[c]
+            while label[r] != r:
+                r = label[r]
+            if r != label[c]:
+                label[c] = r
+                changed = True
+        if not changed:
+            return rounds, label
+    return None, label
+
+
+def rounds_root_hooking(clusters, cap):
+    """The rounds of defuse_amd/csrc/sc_api.hip (k_hook, k_compress) under the lockstep schedule: every element hangs the roots
+    of its clusters' trees under the smallest of them; then every label becomes its root."""
+    label = list(range(len(clusters)))
+    lists = [l for l in element_lists(clusters) if len(l) >= 2]
+
+    def root(lab, c):
+        while lab[c] != c:
+            c = lab[c]
+        return c
+    for rounds in range(1, cap + 1):
+        changed = False
+        src = list(label)
+        for l in lists:
+            roots = [root(src, c) for c in l]
+            m = min(roots)
+            for r in roots:
+                if r > m:
+                    label[r] = min(label[r], m)
+                    changed = True
+        label = [root(label, c) for c in range(len(label))]
+        if not changed:
+            return rounds, label
+    return None, label
+
+
+# root hooking with full compression: the trees of a component halve at least every two rounds (a tree that does not hang
+# itself under a neighbour sees every neighbour hang itself somewhere, and in the round after either follows one of them or
+# has them all), plus the round that finds nothing to do; ceil(log2 n) + 2 is the figure for halving every round.  The tests
+# allow four times that.
+def cc_round_bound(n):
+    return 4 * ((n - 1).bit_length() + 2)
+
+
+def test_label_chain_needs_a_round_per_cluster_when_clusters_are_hooked():
+    """Why label_chain is a case: with hooking by cluster the smallest label advances one cluster per round along the path,
+    under either schedule, so the rounds grow with the length of the chain (and past the 10 000-round cap a valid input was
+    refused); hooking by root does not care about the length."""
+    n = 400
+    for ids in ("down", "up"):
+        clusters = label_chain(n, ids)
+        assert sorted(len(c) for c in clusters) == [2, 2] + [3] * (n - 2)
+        slow, label = rounds_cluster_hooking(clusters, "lockstep", 2 * n)
+        assert slow is not None and slow >= n // 2 and set(label) == {0}, (ids, slow)
+        fast, label = rounds_root_hooking(clusters, 2 * n)
+        assert fast is not None and fast <= cc_round_bound(n) and set(label) == {0}, (ids, fast)
+    slow, _ = rounds_cluster_hooking(label_chain(n, "down"), "serial", 2 * n)      # ascending ids run against the label's way
+    assert slow >= n // 2
+
+
+@pytest.mark.gpu
+def test_gpu_components_of_long_chains(built):
+    """Two chains of 12 000 clusters, one numbered each way, as two components of one call: converges in a number of rounds
+    that does not grow with the chain (cc_round_bound: 64 here), and every owner is the oracle's."""
+    from defuse_amd import sc
+    from oracle import setcover_oracle as o
+    n = 12000
+    clusters = label_chain(n, "down") + label_chain(n, "up", first_element=2 * n - 1)
+    sol, t = sc.cover(clusters)
+    print("cc_iterations", t.cc_iterations, "components_ms", t.components_ms, "greedy_ms", t.greedy_ms)
+    assert t.n_components == 2 and t.n_large == 2
+    assert cc_round_bound(n) == 64 and t.cc_iterations <= 64
+    assert sol == o.set_cover(clusters)
+
+
+# ---- routing (lane kernel / wave kernel) and ties -----------------------------------------------------------------------------
+
+EDGE_SIZES = (1, 2, 31, 32, 33, 63, 64, 65, 129)       # 32 | 33: SMALL_MAX; 64, 65, 129: lane strides of the wave kernel
+FAR_ELEMENT = (1 << 20) - 3
+
+
+def tie_component(k, base, far=None):
+    """One component of exactly k clusters on elements base, base + 1, ...: a three-cluster core on which the tie rules
+    part ([a, b, e], [a, b], [e, f, g]: the last of the two largest goes first and takes e; that decrement makes cluster 0 the
+    most recent of the two that are left with two elements), then exact copies of earlier clusters and near copies (one
+    element more, or one element listed twice), so that most choices are ties and elements sit in three and more clusters.
+    Which clusters are copied is drawn at random, and copies can level the core's difference out again: the first seed is
+    taken whose component still tells both wrong rules of greedy_with_rule from the reference's (components do not touch,
+    so this can be asked of one alone).  Returns (clusters, number of elements used)."""
+    if k == 1:
+        return [[base, base + 1, base]], 2                               # nothing to choose; an element listed twice
+    if k == 2:
+        return [[base, base + 1], [base + 1, base]], 2                   # one choice: which of two equal clusters
+    a, b, e, f, g = range(base, base + 5)
+    for seed in range(200):
+        clusters = [[a, b, e], [a, b], [e, f, g]]
+        nxt = base + 5
+        rng = np.random.default_rng(1000 * k + seed)
+        while len(clusters) < k:
+            src = list(clusters[int(rng.integers(0, len(clusters)))])
+            kind = len(clusters) % 4
+            if kind == 1 and len(src) < 6:
+                src.append(nxt)                                          # near copy: one new element
+                nxt += 1
+            elif kind == 2:
+                src.append(src[int(rng.integers(0, len(src)))])          # near copy: an element twice
+            elif kind == 3:
+                rng.shuffle(src)                                         # exact copy, other order of taking
+            clusters.append(src)
+        if far is not None:
+            clusters[-1].append(far)
+        ref = greedy_with_rule(clusters, "reference")
+        if greedy_with_rule(clusters, "lowest") != ref and greedy_with_rule(clusters, "stale") != ref:
+            return clusters, nxt - base
+    raise AssertionError("no component of %d clusters tells the tie rules apart" % k)
+
+
+def tie_case():
+    """Components of every size in EDGE_SIZES, empty clusters between them, small element ids but one.
+    Returns (clusters, [cluster index range of each component])."""
+    clusters, spans, base = [], [], 0
+    for k in EDGE_SIZES:
+        comp, used = tie_component(k, base, far=FAR_ELEMENT if k == 129 else None)
+        spans.append(range(len(clusters), len(clusters) + k))
+        clusters += comp
+        clusters += [[]] * (1 + k % 3)
+        base += used + 2                                                 # and element ids nobody lists
+    return clusters, spans
+
+
+def greedy_with_rule(clusters, rule):
+    """The greedy of tools/setcover.cpp:30-110 written the slow way, with the tie rule as a parameter: "reference" = among the
+    largest the one that arrived at its size last (arrival refreshed by every decrement); "lowest" = the lowest index
+    among the largest; "stale" = arrival order never refreshed (the highest index among the largest)."""
+    e2c = {}
+    for c, lst in enumerate(clusters):
+        for e in lst:
+            e2c.setdefault(e, []).append(c)
+    size = [len(c) for c in clusters]
+    seq = list(range(1, len(clusters) + 1))
+    counter = len(clusters)
+    sol, owned = [[] for _ in clusters], set()
+    while True:
+        if rule == "lowest":
+            best = max(range(len(clusters)), key=lambda c: (size[c], -c), default=None)
+        else:
+            best = max(range(len(clusters)), key=lambda c: (size[c], seq[c]), default=None)
+        if best is None or size[best] <= 0:
+            return sol
+        for e in clusters[best]:
+            if e in owned:
+                continue
+            owned.add(e)
+            sol[best].append(e)
+            for c2 in e2c[e]:
+                size[c2] -= 1
+                counter += 1
+                if rule != "stale":
+                    seq[c2] = counter
+
+
+def component_count(clusters):
+    """(components, components of more than 32 clusters) by union-find; every cluster is a node, the empty ones too."""
+    parent = list(range(len(clusters)))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    seen = {}
+    for c, lst in enumerate(clusters):
+        for e in lst:
+            if e in seen:
+                parent[find(c)] = find(seen[e])
+            else:
+                seen[e] = c
+    sizes = {}
+    for c in range(len(clusters)):
+        sizes[find(c)] = sizes.get(find(c), 0) + 1
+    return len(sizes), sum(1 for s in sizes.values() if s > 32)
+
+
+def test_tie_case_tells_the_tie_rules_apart():
+    """Precondition of test_gpu_routing_and_ties, on the oracle alone: in every component of the case the oracle's answer
+    is not the answer of either wrong tie rule, so a kernel that breaks ties one of those ways fails there.  (A component of
+    one cluster has no choice to make, and one of two clusters only the first: there a rule cannot show, and the test says so
+    by asserting equality.)"""
+    from oracle import setcover_oracle as o
+    clusters, spans = tie_case()
+    assert [len(s) for s in spans] == list(EDGE_SIZES)
+    exp = o.set_cover(clusters)
+    assert greedy_with_rule(clusters, "reference") == exp
+    lowest, stale = greedy_with_rule(clusters, "lowest"), greedy_with_rule(clusters, "stale")
+    for span in spans:
+        k = len(span)
+        part = lambda sol: [sorted(sol[c]) for c in span]
+        assert (part(lowest) != part(exp)) == (k >= 2), k
+        assert (part(stale) != part(exp)) == (k >= 3), k
+    # what is mixed in
+    assert any(len(set(c)) < len(c) for c in clusters)                               # an element listed twice
+    lists = element_lists(clusters)
+    assert sum(1 for l in lists if len(set(l)) >= 3) > 50                            # elements of three and more clusters
+    assert all(clusters[s[-1] + 1] == [] for s in spans)                             # empty clusters between components
+    els = sorted({e for c in clusters for e in c})
+    assert els[-1] == FAR_ELEMENT and els[-2] < 2000                                 # one far id: a sparse element table
+    n_comp, n_large = component_count(clusters)
+    assert n_large == 5 and n_comp == len(EDGE_SIZES) + sum(1 for c in clusters if not c)
+
+
+@pytest.mark.gpu
+def test_gpu_routing_and_ties(built):
+    from defuse_amd import sc
+    from oracle import setcover_oracle as o
+    clusters, _ = tie_case()
+    sol, t = sc.cover(clusters)
+    assert sol == o.set_cover(clusters)
+    assert (t.n_components, t.n_large) == component_count(clusters)

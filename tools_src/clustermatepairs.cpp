@@ -36,6 +36,36 @@ unsigned pack_ref_bin(int ref, int strand, int bin)   // RefBinPacked (:28-65); 
     return (unsigned)ref | ((unsigned)strand << 18) | (((unsigned)bin & 0x1FFFu) << 19);
 }
 
+// Where AddBinPairs stops on one (alignment, bin), in the reference's order: the RefBinPacked constructor first (:258 —
+// too many reference sequences, then chromosome too large, :33-47), PackAlignment's four DebugChecks after it (:260,
+// :183-186).  Returns false when the pair is fine; else `out` / `err` hold what the reference prints before exit(1).
+bool alignment_stop(int ref, int start, int end, int bin, std::vector<std::string>& out, std::string& err)
+{
+    if (ref >= (1 << 18)) {
+        out = {std::to_string(ref), std::to_string(1 << 18)};
+        err = "Packing failed, too many reference sequences";
+        return true;
+    }
+    if (bin >= (1 << 13)) {
+        out = {std::to_string(bin), std::to_string(1 << 13)};
+        err = "Packing failed, chromosome too large";
+        return true;
+    }
+    const int rs = start - bin * binLength + binLength / 2, re = end - bin * binLength + binLength / 2;
+    // DebugCheckFailure (tools/DebugCheck.cpp:15-19) with the expressions as :183-186 spell them; what __FILE__ was in the
+    // reference's build is not known, the bare file name stands for it
+    const char* expr = nullptr;
+    int line = 0;
+    if (!(rs >= 0)) { expr = "relativeStart >= 0"; line = 183; }
+    else if (!(re >= 0)) { expr = "relativeEnd >= 0"; line = 184; }
+    else if (!(rs < (1 << 16))) { expr = "relativeStart < (1<<16)"; line = 185; }
+    else if (!(re < (1 << 16))) { expr = "relativeEnd < (1 << 16)"; line = 186; }
+    if (!expr) return false;
+    out.clear();
+    err = std::string("Error: ") + expr + " failed on line: " + std::to_string(line) + " of clustermatepairs.cpp";
+    return true;
+}
+
 // r8_normal_01_cdf_inverse (AS 241, tools/asa241.C:424-563)
 double poly(const double* a, double x) { double v = 0.0; for (int i = 7; i >= 0; --i) v = v * x + a[i]; return v; }
 double normal_01_cdf_inverse(double p)
@@ -425,16 +455,8 @@ int main(int argc, char* argv[])
                     const int startBin = (a->region.start - minFusionRange) / binLength, endBin = (a->region.end + minFusionRange) / binLength;
                     for (int b = startBin; b <= endBin; ++b) {
                         const int rs = a->region.start - b * binLength + binLength / 2, re = a->region.end - b * binLength + binLength / 2;
-                        if (rs < 0 || re < 0 || rs >= (1 << 16) || re >= (1 << 16)) {
+                        if (alignment_stop(a->referenceIndex, a->region.start, a->region.end, b, pc.errorStdout, pc.error)) {
                             pc.errorLine = 1;
-                            pc.error = "Error: relativeStart >= 0 failed (alignment does not fit its bin)";
-                            return;
-                        }
-                        if (a->referenceIndex >= (1 << 18) || b >= (1 << 13)) {        // RefBinPacked (:28-65)
-                            const bool refs = a->referenceIndex >= (1 << 18);
-                            pc.errorLine = 1;
-                            pc.errorStdout = {std::to_string(refs ? a->referenceIndex : b), std::to_string(refs ? (1 << 18) : (1 << 13))};
-                            pc.error = refs ? "Packing failed, too many reference sequences" : "Packing failed, chromosome too large";
                             return;
                         }
                         binned[a->readEnd].push_back(std::make_pair(pack_ref_bin(a->referenceIndex, a->strand, b),
@@ -551,11 +573,15 @@ int main(int argc, char* argv[])
             unsigned t = 0;
             while (t + 1 < nThreads && (size_t)st.err_record >= recBase[t + 1]) ++t;
             const cmp_record& a = pieces[t].recs[(size_t)st.err_record - recBase[t]];
-            if (st.err_kind == 1) die("Error: relativeStart >= 0 failed (alignment does not fit its bin)");
-            const bool refs = st.err_kind == 2;
-            const int startBin = (a.start - minFusionRange) / binLength;
-            std::cout << (refs ? (int)(a.meta & 0x0FFFFFFFu) : std::max(startBin, 1 << 13)) << std::endl << (refs ? (1 << 18) : (1 << 13)) << std::endl;
-            die(refs ? "Packing failed, too many reference sequences" : "Packing failed, chromosome too large");
+            // (the first of its bins that stops, walked again here: the device names the record and the kind)
+            const int startBin = (a.start - minFusionRange) / binLength, endBin = (a.end + minFusionRange) / binLength;
+            std::vector<std::string> lines;
+            std::string message;
+            for (int b = startBin; b <= endBin; ++b)
+                if (alignment_stop((int)(a.meta & 0x0FFFFFFFu), a.start, a.end, b, lines, message)) break;
+            if (message.empty()) die("Error: bin pairs on the GPU failed: a stop condition that the host does not find");
+            for (const std::string& l : lines) std::cout << l << std::endl;
+            die(message);
         }
         if (device_problems) {
             std::vector<int> devs = devices_from_env();
