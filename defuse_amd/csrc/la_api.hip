@@ -14,6 +14,7 @@
 //           With a minimum score per pair (the tool's -t threshold) it prunes exactly, as the split-read fill
 //           does: a cell with H + max(match,0)*(rows left) < need cannot lie on the path to a score >= need, so
 //           once a whole row group of a tile and the boundary entering it are dead the tile is left.
+//           Every wave adds the row groups it swept (over its tiles) to one 64-bit counter: la_timing.row_groups16.
 //   k_la32: one pair per lane in int32, any scores, padded columns masked out of the maximum.
 //
 // Pairs are sorted by (sequence length, reference length) so that the lanes of a wave sweep about the
@@ -176,7 +177,8 @@ __global__ void k_pack_win(const uint8_t* __restrict__ genome, const uint8_t* __
 __global__ __launch_bounds__(WG_WAVES * WAVE, 2) void k_la16(const Lane* __restrict__ lanes, const Wave* __restrict__ waves, int n_waves,
                                                            const uint32_t* __restrict__ refcodes,
                                                            const uint32_t* __restrict__ rowcodes, uint32_t* __restrict__ bnd,
-                                                           Params prm, int32_t* __restrict__ scores)
+                                                           Params prm, int32_t* __restrict__ scores,
+                                                           unsigned long long* __restrict__ row_groups)
 {
     const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WG_WAVES + (threadIdx.x >> 6)));
     if (w >= n_waves) return;
@@ -217,6 +219,7 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 2) void k_la16(const Lane* __restr
     };
     int l_in = wave_max(max(rows_alive_at_zero(base0, ln.ls[0]), rows_alive_at_zero(base1, ln.ls[1])));
     int stop_prev = 0;
+    unsigned long long swept = 0;           // row groups this wave swept, all tiles (wave-uniform)
 
     for (int c = 0; c < wv.nch; ++c) {
         uint32_t r[W];
@@ -284,8 +287,10 @@ __global__ __launch_bounds__(WG_WAVES * WAVE, 2) void k_la16(const Lane* __restr
             if (4 * gq + 3 > l_in && __builtin_amdgcn_ballot_w64(alive_bits != 0u) == 0) { ++gq; break; }   // wave-uniform
         }
         stop_prev = gq;
+        swept += (unsigned long long)gq;
         l_in = wave_max(last_bnd);
     }
+    if (lane == 0) atomicAdd(row_groups, swept);
     if (ln.out[0] >= 0) scores[ln.out[0]] = best0;
     if (ln.out[1] >= 0) scores[ln.out[1]] = best1;
 }
@@ -370,7 +375,7 @@ inline int32_t ref_len(const la_item& it) { return it.ref_len; }
 inline int32_t ref_len(const la_window& wd) { return wd.pad_left + wd.slice_len + wd.pad_right; }
 
 template <class Item>
-void add_wave(Group& g, const Item* items, const int32_t* min_score, const int64_t* order, int64_t n, int items_per_lane)
+void add_wave(Group& g, const Params& prm, const Item* items, const int32_t* min_score, const int64_t* order, int64_t n, int items_per_lane)
 {
     Wave wv{};
     wv.ref_off = g.ref_dwords;
@@ -388,7 +393,12 @@ void add_wave(Group& g, const Item* items, const int32_t* min_score, const int64
                 ln.out[f] = (int32_t)order[k];
                 ln.lr[f] = ref_len(it);
                 ln.ls[f] = it.seq_len;
-                if (min_score) ln.need[f] = std::max(min_score[order[k]], NO_NEED);
+                if (min_score) {
+                    // no score exceeds mp * seq_len: a minimum above it is as unreachable one above it, and the kernel's
+                    // thresholds (need - mp*ls + slope*j + BIAS) then stay far inside int
+                    const int64_t top = (int64_t)prm.mp * it.seq_len + 1;
+                    ln.need[f] = (int32_t)std::max<int64_t>(std::min<int64_t>(min_score[order[k]], top), NO_NEED);
+                }
                 lr_max = std::max(lr_max, ln.lr[f]);
                 ls_max = std::max(ls_max, it.seq_len);
             }
@@ -447,9 +457,12 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
     DeviceBuffer<uint8_t> d_pool;
     DeviceBuffer<Item> d_items;
     DeviceBuffer<int32_t> d_scores;
+    DeviceBuffer<unsigned long long> d_row_groups;      // what k_la16 swept in this call
     HIPL(d_pool.reserve((size_t)pool_len));
     HIPL(d_items.reserve((size_t)n_items));
     HIPL(d_scores.reserve((size_t)n_items));
+    HIPL(d_row_groups.reserve(1));
+    HIPL(hipMemset(d_row_groups.p, 0, sizeof(unsigned long long)));
     if (pool_len > 0) HIPL(hipMemcpy(d_pool.p, pool, (size_t)pool_len, hipMemcpyHostToDevice));
     HIPL(hipMemcpy(d_items.p, items, (size_t)n_items * sizeof(Item), hipMemcpyHostToDevice));
     hiphost::Event ev[3];                 // destroyed on every return
@@ -465,7 +478,7 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
             Group g;
             while (k < end) {
                 const int64_t n = std::min(per_wave, end - k);
-                add_wave(g, items, min_score, order.data() + k, n, items_per_lane);
+                add_wave(g, prm, items, min_score, order.data() + k, n, items_per_lane);
                 k += n;
                 if ((size_t)(g.ref_dwords + g.row_dwords + g.bnd_dwords) >= budget_dwords) break;
             }
@@ -486,7 +499,7 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
             const unsigned grid = hiphost::grid_of(n_waves, WG_WAVES);
             if (items_per_lane == 2)
                 hipLaunchKernelGGL(k_la16, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
-                                   d_bnd.p, prm, d_scores.p);
+                                   d_bnd.p, prm, d_scores.p, d_row_groups.p);
             else
                 hipLaunchKernelGGL(k_la32, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
                                    d_bnd.p, prm, d_scores.p);
@@ -505,6 +518,9 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
     if (rc == DSA_OK) rc = run_range(first16, n_items, 2);
     if (rc != DSA_OK) return rc;
     HIPL(hipMemcpy(scores, d_scores.p, (size_t)n_items * sizeof(int32_t), hipMemcpyDeviceToHost));
+    unsigned long long row_groups = 0;
+    HIPL(hipMemcpy(&row_groups, d_row_groups.p, sizeof row_groups, hipMemcpyDeviceToHost));
+    tm.row_groups16 = (int32_t)std::min<unsigned long long>(row_groups, (unsigned long long)INT32_MAX);
     return DSA_OK;
 }
 

@@ -10,7 +10,7 @@ LA_ITEM = np.dtype([("ref_off", np.int64), ("seq_off", np.int64), ("ref_len", np
 
 class LaTiming(ctypes.Structure):
     _fields_ = [("pack_ms", ctypes.c_float), ("kernel_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
-                ("n_packed16", ctypes.c_int32), ("n_int32", ctypes.c_int32), ("pad_", ctypes.c_int32),
+                ("n_packed16", ctypes.c_int32), ("n_int32", ctypes.c_int32), ("row_groups16", ctypes.c_int32),
                 ("cells", ctypes.c_int64)]
 
 

@@ -37,7 +37,9 @@ typedef struct la_timing {
     float   total_ms;
     int32_t n_packed16;  /* pairs scored by the packed 16-bit kernel */
     int32_t n_int32;     /* pairs scored by the int32 kernel         */
-    int32_t pad_;
+    int32_t row_groups16; /* row groups (4 rows of one 64-column tile of one wave) the packed kernel swept, saturated at
+                           * INT32_MAX.  Without a minimum score: the sum over its waves of tiles * (longest sequence / 4 + 1);
+                           * with one, what the pruning left.  The int32 kernel does not count. */
     int64_t cells;       /* sum of (ref_len+1)*(seq_len+1)           */
 } la_timing;
 

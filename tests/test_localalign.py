@@ -125,11 +125,13 @@ def test_gpu_minimum_scores(built):
     the others only have to stay below it."""
     from defuse_amd import la
     from oracle import localalign_oracle as o
+    from tests import la_sweep_model
     pairs = random_pairs(51, 3000, lr=(50, 700), ls=(20, 260), related=0.5)
     want = np.array([o.simple_align(*PIPELINE, r, s) for r, s in pairs], dtype=np.int64)
     for frac in (0.8, 0.5, 1.0):
         need = np.array([int(np.ceil(frac * 10 * len(s))) for _, s in pairs], dtype=np.int32)
-        got, _ = la.align_batch(pairs, *PIPELINE, min_score=need)
+        got, t = la.align_batch(pairs, *PIPELINE, min_score=need)
+        assert 0 < t.row_groups16 < la_sweep_model.closed_form(pairs, *PIPELINE)      # pruning is on
         hit = want >= need
         assert hit.sum() > 20 and (~hit).sum() > 100
         assert np.array_equal(got[hit], want[hit])
