@@ -1214,7 +1214,8 @@ __device__ __forceinline__ int sweep_tile_generic(const uint32_t (&r)[WT], const
 
 // After the last tile: rmax = max over tiles of cmax (both fields), so the combine step reads one
 // dword per row instead of one per tile.  A tile is read only up to its stop: its rows past it stand for
-// V = 0 (BIAS2), the accumulator's initial value, so leaving them out is exact.  cmax of this wave is L2-hot.
+// V = 0 (BIAS2), the accumulator's initial value, so leaving them out is exact.  cmax of this wave is L2-hot,
+// and what the reduction costs is the waiting for it, not its instructions (profiles/tail_wait).
 __device__ __forceinline__ void max4(uint4& m, const uint4& v)
 {
     m.x = max2(m.x, v.x);
@@ -1225,6 +1226,9 @@ __device__ __forceinline__ void max4(uint4& m, const uint4& v)
 // WIDE: with the in-register path for 9 to 16 tiles.  It is a template parameter of the fill kernels (the host picks the
 // instantiation by the slice's tile count) because its mere presence in a kernel costs the sweep of the common, narrower
 // shapes 4 % — the compiler's schedule of the sweep loop is sensitive to what else the kernel holds (profiles/r04/ab_rm16.txt).
+#ifndef RMAX_SETS
+#define RMAX_SETS 3             // register sets of eight row-group loads the reduction of up to eight tiles keeps in turn
+#endif
 template <bool WIDE>
 __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax, uint32_t* __restrict__ rmax,
                                                const int32_t* tstop, const TileStops& stops,
@@ -1236,44 +1240,83 @@ __device__ __forceinline__ void reduce_row_max(const uint32_t* __restrict__ cmax
     const uint4* src = reinterpret_cast<const uint4*>(cmax + (int64_t)w * g.nch * g.lq1 * WAVE) + lane;
     const int64_t cstride = (int64_t)(g.lq1 >> 2) * WAVE;       // uint4 elements between two tiles
     constexpr int NC = 8;
-    if (nch_wave <= NC) {
-        // the live tiles of a row group in registers: one round of independent loads, then the maximum (the branches
-        // are wave-uniform; a tile past the wave's last has stop 0)
-        for (int gq = 0; gq < ngq; ++gq) {
-            uint4 v[NC];
+    // Up to 16 tiles in registers, eight loads a round, issued together and without a branch: a tile that is dead at the row
+    // group (at or past its stop; a tile past the wave's last has stop 0) reads the row group of the wave's longest-lived
+    // tile instead - the base pointer is picked with the wave-uniform condition, and a maximum taken twice is the same
+    // maximum.  Row groups past every stop are stored without a load.  The loads of the next rounds are on their way while
+    // a round is reduced, as the sweep does with its boundary and row codes: RMAX_SETS - 1 row groups ahead for up to
+    // eight tiles (three sets: fill -1.3 %, two: -1.0 %; four would be every register the kernel has), one round for WIDE.
+    const char* planes = reinterpret_cast<const char*>(cmax + (int64_t)w * g.nch * g.lq1 * WAVE);   // uniform; the lane's part is an offset
+    const int64_t tile_bytes = cstride * (int64_t)sizeof(uint4);
+    auto issue = [&](uint4 (&v)[NC], const int (&st)[NC], int c0, int gq, const char* alive_tile) {
+        const uint32_t at = (uint32_t)(gq * WAVE + lane) * (uint32_t)sizeof(uint4);
 #pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (gq < stops.v[c]) v[c] = src[c * cstride + (int64_t)gq * WAVE];
-            uint4 m = dead4;
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (gq < stops.v[c]) max4(m, v[c]);
-            out[(int64_t)gq * WAVE] = m;
+        for (int c = 0; c < NC; ++c) {
+            const char* tile = gq < st[c] ? planes + (c0 + c) * tile_bytes : alive_tile;      // uniform
+            v[c] = load_group(reinterpret_cast<const uint4*>(tile + at));
         }
+    };
+    auto fold = [](uint4& m, const uint4 (&v)[NC]) {
+#pragma unroll
+        for (int c = 0; c < NC; c += 2) {
+            m.x = max3(m.x, v[c].x, v[c + 1].x);
+            m.y = max3(m.y, v[c].y, v[c + 1].y);
+            m.z = max3(m.z, v[c].z, v[c + 1].z);
+            m.w = max3(m.w, v[c].w, v[c + 1].w);
+        }
+    };
+    auto longest = [](const int (&st)[NC], int c0, int& smax, int& cbest) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            if (st[c] > smax) { smax = st[c]; cbest = c0 + c; }
+    };
+    if (nch_wave <= NC) {
+        int smax = 0, cbest = 0;
+        longest(stops.v, 0, smax, cbest);
+        smax = smax < ngq ? smax : ngq;
+        const char* alive_tile = planes + cbest * tile_bytes;
+        uint4 v[RMAX_SETS][NC];                             // a ring of register sets: RMAX_SETS - 1 row groups ahead
+        if (smax > 0) {
+#pragma unroll
+            for (int d = 0; d < RMAX_SETS - 1; ++d) issue(v[d], stops.v, 0, d < smax ? d : smax - 1, alive_tile);
+        }
+        for (int g0 = 0; g0 < smax; g0 += RMAX_SETS) {      // RMAX_SETS row groups a turn: the sets take turns
+#pragma unroll
+            for (int d = 0; d < RMAX_SETS; ++d) {
+                const int gq = g0 + d, ahead = gq + RMAX_SETS - 1;
+                if (gq >= smax) break;                      // uniform
+                issue(v[(d + RMAX_SETS - 1) % RMAX_SETS], stops.v, 0, ahead < smax ? ahead : smax - 1, alive_tile);
+                uint4 m = dead4;
+                fold(m, v[d]);
+                out[(int64_t)gq * WAVE] = m;
+            }
+        }
+        for (int gq = smax; gq < ngq; ++gq) out[(int64_t)gq * WAVE] = dead4;
         return;
     }
     if (WIDE && nch_wave <= 2 * NC) {
-        // 9 to 16 tiles (2x150 bp: windows of 590 bases are ten tiles): the same in two rounds of eight, the stops of the tiles
-        // beyond the eighth read back (wave-uniform).  With the tile-by-tile loop below this reduction was 37 % of the fill
-        // kernel's wave cycles at 2x150 (profiles/r04/mix_stats.txt).
+        // 9 to 16 tiles (2x150 bp: windows of 590 bases are ten tiles): two rounds of eight per row group, the stops of the
+        // tiles beyond the eighth read back (wave-uniform).  With the tile-by-tile loop below this reduction was 37 % of the
+        // fill kernel's wave cycles at 2x150 (profiles/r04/mix_stats.txt).
         int stop_hi[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) stop_hi[c] = NC + c < nch_wave ? uniform(load_tstop(tstop + (int64_t)w * g.nch + NC + c)) : 0;
-        for (int gq = 0; gq < ngq; ++gq) {
-            uint4 v[NC], u[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if (gq < stops.v[c]) v[c] = src[c * cstride + (int64_t)gq * WAVE];
-                if (gq < stop_hi[c]) u[c] = src[(NC + c) * cstride + (int64_t)gq * WAVE];
-            }
+        int smax = 0, cbest = 0;
+        longest(stops.v, 0, smax, cbest);
+        longest(stop_hi, NC, smax, cbest);
+        smax = smax < ngq ? smax : ngq;
+        const char* alive_tile = planes + cbest * tile_bytes;
+        uint4 va[NC], vb[NC];
+        if (smax > 0) issue(va, stops.v, 0, 0, alive_tile);
+        for (int gq = 0; gq < smax; ++gq) {
+            issue(vb, stop_hi, NC, gq, alive_tile);
             uint4 m = dead4;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                if (gq < stops.v[c]) max4(m, v[c]);
-                if (gq < stop_hi[c]) max4(m, u[c]);
-            }
+            fold(m, va);
+            issue(va, stops.v, 0, gq + 1 < smax ? gq + 1 : gq, alive_tile);
+            fold(m, vb);
             out[(int64_t)gq * WAVE] = m;
         }
+        for (int gq = smax; gq < ngq; ++gq) out[(int64_t)gq * WAVE] = dead4;
         return;
     }
     for (int gq = 0; gq < ngq; ++gq) {
