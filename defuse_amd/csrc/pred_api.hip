@@ -130,23 +130,6 @@ __global__ __launch_bounds__(BLOCK) void k_pred_segments(const eval_group* __res
 
 }  // namespace
 
-struct __attribute__((visibility("hidden"))) pred_ctx {
-    int device = -1;
-    hiphost::Stream st;
-    hiphost::Event ev[7];       // 0 start, 1 groups uploaded, 2 plan done, 3 descriptors done, 4 gathers done; 5, 6 around a fetch
-    // the results
-    int64_t n_results = 0, seq_bytes_len = 0;
-    DeviceBuffer<pred_result, GrowSize> results;
-    DeviceBuffer<uint8_t, GrowSize> seq_bytes;
-    // per call
-    DeviceBuffer<eval_group, GrowSize> groups;
-    DeviceBuffer<u64, GrowSize> len, off;
-    DeviceBuffer<uint32_t, GrowSize> tidx;
-    DeviceBuffer<Seg64, GrowSize> seg_rem, seg_win;
-    DeviceBuffer<uint8_t, GrowSize> tmp;
-    pred_timing timing{};
-};
-
 namespace {
 
 // everything after the groups are on the device (c->ev[1] recorded)
@@ -189,6 +172,7 @@ int predict_on_device(pred_ctx* c, const pred_tasks* t, const eval_group* groups
     PRED_HIP(hipGetLastError());
     c->n_results = n;
     c->seq_bytes_len = SB;
+    c->predicted = true;
     c->timing.plan_ms = hiphost::elapsed(c->ev[1], c->ev[2]);
     c->timing.scan_ms = hiphost::elapsed(c->ev[2], c->ev[3]);
     c->timing.gather_ms = hiphost::elapsed(c->ev[3], c->ev[4]);
@@ -207,12 +191,16 @@ int predict(const char* what, pred_ctx* c, const pred_tasks* t, const eval_group
         return PRED_FAIL(DSA_E_ARG, "%s: ctx, tasks and groups are on devices %d, %d and %d", what, c->device, t->device,
                          on_device ? groups_device_ordinal : c->device);
     c->n_results = c->seq_bytes_len = 0;
+    c->predicted = false;
     c->timing = pred_timing{0, 0, 0, 0, 0, 0, n, 0};
     PRED_HIP(hipSetDevice(c->device));
     // the view of empty results has pointers too
     PRED_HIP(c->results.reserve(1));
     PRED_HIP(c->seq_bytes.reserve(4));
-    if (n == 0) return DSA_OK;
+    if (n == 0) {
+        c->predicted = true;
+        return DSA_OK;
+    }
     hipStream_t st = c->st;
     PRED_HIP(hipEventRecord(c->ev[0], st));
     if (!on_device) {
@@ -246,6 +234,7 @@ void clear(pred_ctx* ctx)
 {
     if (!ctx) return;
     ctx->n_results = ctx->seq_bytes_len = 0;
+    ctx->predicted = false;
     ctx->timing = pred_timing{};
 }
 

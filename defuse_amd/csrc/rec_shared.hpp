@@ -80,6 +80,33 @@ REC_HD int rec_write_field(int32_t v, Char* out)
     return p + d + 1;
 }
 
+// The same for a 64-bit value ("%lld\t"; ptext_shared.hpp prints a group's count with it): 1..19 digits.
+REC_HD uint64_t rec_magnitude64(int64_t v) { return v < 0 ? 0ull - (uint64_t)v : (uint64_t)v; }
+
+REC_HD int rec_digits64(uint64_t m)
+{
+    if (m < 10000000000ull) return m <= 0xFFFFFFFFull ? rec_digits((uint32_t)m) : 10;
+    return 10 + rec_digits((uint32_t)(m / 10000000000ull));          // (m / 10^10 < 2^31)
+}
+
+REC_HD int rec_field_length64(int64_t v) { return rec_digits64(rec_magnitude64(v)) + (v < 0 ? 1 : 0) + 1; }
+
+template <typename Char>
+REC_HD int rec_write_field64(int64_t v, Char* out)
+{
+    uint64_t m = rec_magnitude64(v);
+    int p = 0;
+    if (v < 0) out[p++] = '-';
+    const int d = rec_digits64(m);
+    for (int k = d - 1; k >= 0; --k) {
+        const uint64_t q = m / 10u;
+        out[p + k] = (Char)('0' + (uint32_t)(m - q * 10u));
+        m = q;
+    }
+    out[p + d] = '\t';
+    return p + d + 1;
+}
+
 // the nine printed ints of a record, in print order
 REC_HD const int32_t* rec_fields(const dsa_record& r) { return reinterpret_cast<const int32_t*>(&r); }
 

@@ -7,7 +7,7 @@
  *     the two break positions    tools/SplitAlignment.cpp:553-569   -> pred_predict*, the plan
  *     the two averages           tools/SplitAlignment.cpp:589-591   -> pred_predict*, the plan
  *
- * It is the last link of the resident chain (cand_enumerate_device, bat_assemble_device, dsa_upload_device / dsa_run,
+ * It follows eval in the resident chain (cand_enumerate_device, bat_assemble_device, dsa_upload_device / dsa_run,
  * dsa_copy_records_device, eval_groups_device): the windows that bat_windows_create put on the device are read in place, so
  * a caller of the chain keeps no host copy of them, and what comes down is what WriteSequence and WriteBreak print.
  *
@@ -35,8 +35,8 @@
  * Plain C types; host pointers unless the name says _device.  Returns 0 on success, negative on failure (codes of
  * defuse_dsa.h).  There is no CPU path: creating an object fails with DSA_E_DEVICE without a GPU.  Argument errors that can
  * be told from the arguments alone are found before a device is touched.  One object must not be used from two threads at
- * once.  Out of scope: the tools (they keep their host evaluators), text formatting on the device, more than one GPU per
- * chain, a streamed entry.
+ * once.  Out of scope: the tools (they keep their host evaluators), more than one GPU per chain, a streamed entry.  The
+ * two texts themselves are printed on the device by defuse_ptext.h.
  */
 #ifndef DEFUSE_PRED_H_
 #define DEFUSE_PRED_H_

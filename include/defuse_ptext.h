@@ -1,0 +1,135 @@
+/*
+ * defuse_ptext.h — C ABI of the MI355X prediction text ("ptext"): splitreads.seq and splitreads.break as finished bytes.
+ *
+ * Replaces, for all groups of a prediction at once, the two writers that follow SplitAlignmentTask::Evaluate:
+ *
+ *     WriteSequence    tools/SplitAlignment.cpp:596-605   -> ptext_format, the .seq text
+ *     WriteBreak       tools/SplitAlignment.cpp:607-615   -> ptext_format, the .break text
+ *
+ * It ends the resident chain (cand_enumerate_device, bat_assemble_device, dsa_upload_device / dsa_run,
+ * dsa_copy_records_device, rec_*, eval_groups_device, pred_predict_resident): with rec_text for splitreads.alignments and
+ * splitreads.predalign, a caller of the chain sends alignments up and gets the bytes of all three files down, and keeps no
+ * formatting code and no loop over the groups.
+ *
+ * Per group g of the latest successful pred_predict* of a pred_ctx, in group order:
+ *     .seq    "%d\t" fusion_id, the sequence bytes, "\t0\t", "%lld\t" count, %g(pos_avg), "\t", %g(min_avg), "\n"
+ *     .break  for cluster end 0, then 1:  "%d\t%d\t" fusion_id, end, the end's reference name, "\t+\t" or "\t-\t" by the end's
+ *             ALIGN strand (mAlignStrand of the regions file; not pred_task.seq_strand), "%d\n" break_pos[end]
+ * "%g" is an ostream's default print of a double: precision 6, the text glibc's printf("%g") gives in the C locale.
+ *
+ * Which groups get which lines:
+ *   - EVAL_NO_SPLIT and a task: the tool's lines of a group without a split - sequence "N", count 0, "-1" and "-1", break
+ *     positions 0;
+ *   - PRED_NO_TASK or PRED_OUT_OF_WINDOW: no line in either text (the reference evaluates a default task or exits there);
+ *   - EVAL_HOST_STATS (with a split), or an average the formatter does not take (below): the .break lines, but no .seq
+ *     line, because the sums are the caller's; the group's row gets PTEXT_HOST_SEQ and the caller splices its own line in
+ *     at seq_off of the row.
+ * The formatter takes +-0 and every finite double with 2^-64 <= |x| < 2^64, which covers every average of a group that
+ * eval_groups* did not flag (0, or in [2^-63, 2^31]), and declines everything else: NaN, the infinities, denormals.
+ * Nothing is written for a missing line, and every byte of either text belongs to exactly one line: the lines lie one
+ * after the other in group order, the offsets of the line table are the 64-bit running sums of the lengths (a missing
+ * line has length 0 and the offset of the next one), and either text may pass 2^31 bytes.
+ *
+ * Plain C types; host pointers unless the name says _device.  Returns 0 on success, negative on failure (codes of
+ * defuse_dsa.h).  There is no CPU path: creating an object fails with DSA_E_DEVICE without a GPU.  Argument errors that can
+ * be told from the arguments alone are found before a device is touched.  One object must not be used from two threads at
+ * once.  Out of scope: the tools (they keep their host formatters), the NaN and infinity texts of EVAL_HOST_STATS groups,
+ * more than one GPU per chain, a streamed entry, locales other than C.
+ */
+#ifndef DEFUSE_PTEXT_H_
+#define DEFUSE_PTEXT_H_
+
+#include <stdint.h>
+
+#include "defuse_dsa.h"
+#include "defuse_pred.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PTEXT_HOST_SEQ  16  /* or-ed into the group's EVAL_* / PRED_* bits: .break lines, and the .seq line is the caller's */
+
+/* The reference name and align strand of one cluster end of one fusion. */
+typedef struct ptext_end {
+    int32_t fusion_id;
+    int32_t cluster_end;               /* 0 / 1                                                                        */
+    int32_t name;                      /* mAlignRefName is name_bytes[name_off[name] .. name_off[name + 1])            */
+    int32_t strand;                    /* mAlignStrand: 0 = PlusStrand, 1 = MinusStrand                                */
+} ptext_end;
+
+/* One group's lines: the .seq line is seq_text[seq_off .. seq_off + seq_len), the two .break lines together are
+ * brk_text[brk_off .. brk_off + brk_len).  A length of 0: the group has no such line. */
+typedef struct ptext_line {
+    int64_t seq_off;
+    int64_t seq_len;                   /* (a sequence of 2^31 - 1 bytes makes a longer line)                           */
+    int64_t brk_off;
+    int64_t brk_len;
+    int32_t status;                    /* the group's EVAL_* and PRED_* bits, or-ed with PTEXT_HOST_SEQ                */
+    int32_t pad_;
+} ptext_line;
+
+/* The texts of the latest ptext_format of a ctx on the device.  Valid until the next ptext_format on the ctx or its
+ * destruction. */
+typedef struct ptext_device_view {
+    const void* seq_text;              /* device pointers, never NULL after a successful call                          */
+    const void* brk_text;
+    const void* lines;                 /* ptext_line[n_lines]                                                          */
+    int64_t seq_text_len;
+    int64_t brk_text_len;
+    int64_t n_lines;
+    int32_t device;
+    int32_t pad_;
+} ptext_device_view;
+
+/* HIP-event times of the most recent ptext_format of a ctx, and of the most recent ptext_fetch after it. */
+typedef struct ptext_timing {
+    float   lengths_ms;                /* the line lengths, the two 64-bit sums, the totals to the host                */
+    float   write_ms;                  /* heads, tails, all .break bytes, the line table, the copy descriptors         */
+    float   gather_ms;                 /* the sequences into the .seq text                                             */
+    float   download_ms;               /* ptext_fetch                                                                  */
+    int64_t n_groups;
+    int64_t seq_text_bytes;
+    int64_t brk_text_bytes;
+    int64_t gather_bytes;              /* bytes of the .seq text that the gather wrote                                 */
+} ptext_timing;
+
+typedef struct ptext_names ptext_names;     /* opaque: the names and align strands of a run on one device         */
+typedef struct ptext_ctx ptext_ctx;         /* opaque: the output buffers of one caller, reused call after call   */
+
+/* The name table of a run and its cluster ends, in any order; everything is copied, the caller's buffers are free on
+ * return.  name_off has n_names + 1 ascending offsets into name_bytes; an empty name is allowed.  DSA_E_ARG, naming the
+ * record, for a name that begins below 0, ends before it begins or ends outside name_bytes, for an end with a cluster_end
+ * or a strand other than 0 / 1 or a name outside the table, and for two ends with one (fusion_id, cluster_end).
+ * n_names = 0 and n_ends = 0 are allowed. */
+int ptext_names_create(int device, const uint8_t* name_bytes, int64_t name_bytes_len, const int64_t* name_off, int64_t n_names,
+                       const ptext_end* ends, int64_t n_ends, ptext_names** out);
+void ptext_names_destroy(ptext_names* names);
+
+int ptext_create(int device, ptext_ctx** out);
+void ptext_destroy(ptext_ctx* ctx);
+
+/* Both texts and one ptext_line per group of the latest pred_predict* of `pred`, left on the device in the buffers of
+ * `ctx`, which grow as needed and are kept.  `pred` is read in place and must not run a prediction during the call.  After
+ * a failure both texts and the line table are empty.  DSA_E_ARG: an object is missing, the objects are not on one device,
+ * `pred` has no completed prediction (none yet, or its latest call failed), or a group that gets lines has a cluster end
+ * without an entry in `names`; the error names the lowest such group. */
+int ptext_format(ptext_ctx* ctx, const pred_ctx* pred, const ptext_names* names);
+
+int ptext_view(const ptext_ctx* ctx, ptext_device_view* out);
+/* Downloads the two texts and the line table (a buffer whose capacity is 0 may be NULL).  DSA_E_CAPACITY if one of them
+ * does not fit; nothing is written then.  Capacities are in elements: bytes, bytes, ptext_line. */
+int ptext_fetch(ptext_ctx* ctx, uint8_t* seq_text, int64_t seq_cap, uint8_t* brk_text, int64_t brk_cap, ptext_line* lines, int64_t lines_cap);
+int ptext_get_timing(const ptext_ctx* ctx, ptext_timing* out);
+
+/* The "%g" texts of x[0 .. n) as the device build of the formatter prints them, back to back in out[0 .. *out_len);
+ * len[k] is the length of the k-th text, 0 where the formatter declines.  *out_len always receives the total on success
+ * and on DSA_E_CAPACITY (total > cap; out and len are not written then).  DSA_E_LIMIT: n > 2^30 - 1. */
+int ptext_format_doubles(int device, const double* x, int64_t n, uint8_t* out, int64_t cap, int32_t* len, int64_t* out_len);
+
+const char* ptext_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
