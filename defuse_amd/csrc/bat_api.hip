@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/defuse_bat.h"
+#include "../../include/defuse_text.h"     // bat_reads_create_device
 #include "bat_shared.hpp"
 #include "hip_host.hpp"
 
@@ -95,6 +96,16 @@ __global__ void k_reads_unique(const uint32_t* __restrict__ key, const uint32_t*
     ukey[pos[i]] = key[i];
     uoff[pos[i]] = r.off;
     ulen[pos[i]] = r.len;
+}
+
+// bat_reads_create's per-record checks for records that are on the device: the lowest bad one
+__global__ void k_reads_check(const bat_read* __restrict__ rec, int64_t n, int64_t bytes_len, uint32_t* __restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const bat_read r = rec[i];
+    if (r.fragment < 0 || (r.read_end != 0 && r.read_end != 1) || r.len < 0 || r.off < 0 || r.off > bytes_len || (int64_t)r.len > bytes_len - r.off)
+        atomicMin(bad, (uint32_t)i);
 }
 
 struct ReadsView {
@@ -246,14 +257,29 @@ struct bat_batch {
 
 namespace {
 
+// why bat_reads_create refuses a record, "" if it does not
+std::string read_fault(const bat_read& r, long long k, int64_t bytes_len)
+{
+    char buf[160] = "";
+    if (r.fragment < 0) snprintf(buf, sizeof buf, "read %lld: fragment %d is outside [0, 2^31)", k, r.fragment);
+    else if (r.read_end != 0 && r.read_end != 1) snprintf(buf, sizeof buf, "read %lld: read_end %d is not 0 or 1", k, r.read_end);
+    else if (r.len < 0) snprintf(buf, sizeof buf, "read %lld: negative length %d", k, r.len);
+    else if (r.off < 0 || r.off > bytes_len || (int64_t)r.len > bytes_len - r.off)
+        snprintf(buf, sizeof buf, "read %lld: bytes %lld + %d are outside the %lld given", k, (long long)r.off, r.len, (long long)bytes_len);
+    return buf;
+}
+
+// DEVICE: bytes and reads are device pointers of the store's GPU, and the records are checked here, by a kernel
+template <bool DEVICE>
 int reads_build(bat_reads* r, const uint8_t* bytes, const bat_read* reads, int64_t n)
 {
     hipStream_t st = r->st;
+    const hipMemcpyKind kind = DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     BAT_HIP(r->bytes.reserve((size_t)r->bytes_len + SRC_PAD));
     BAT_HIP(r->ukey.reserve(1));
     BAT_HIP(r->uoff.reserve(1));
     BAT_HIP(r->ulen.reserve(1));
-    if (r->bytes_len) BAT_HIP(hipMemcpyAsync(r->bytes.p, bytes, (size_t)r->bytes_len, hipMemcpyHostToDevice, st));
+    if (r->bytes_len) BAT_HIP(hipMemcpyAsync(r->bytes.p, bytes, (size_t)r->bytes_len, kind, st));
     if (n == 0) {
         BAT_HIP(hipStreamSynchronize(st));
         return DSA_OK;
@@ -268,7 +294,21 @@ int reads_build(bat_reads* r, const uint8_t* bytes, const bat_read* reads, int64
     BAT_HIP(idx_sorted.reserve((size_t)n));
     BAT_HIP(flag.reserve((size_t)n));
     BAT_HIP(pos.reserve((size_t)n));
-    BAT_HIP(hipMemcpyAsync(rec.p, reads, (size_t)n * sizeof(bat_read), hipMemcpyHostToDevice, st));
+    BAT_HIP(hipMemcpyAsync(rec.p, reads, (size_t)n * sizeof(bat_read), kind, st));
+    if (DEVICE) {
+        uint32_t bad = NONE;
+        BAT_HIP(hipMemcpyAsync(flag.p, &bad, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_reads_check, dim3(grid_of(n)), dim3(BLOCK), 0, st, (const bat_read*)rec.p, n, r->bytes_len, flag.p);
+        BAT_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        BAT_HIP(hipStreamSynchronize(st));
+        BAT_HIP(hipGetLastError());
+        if (bad != NONE) {
+            if ((int64_t)bad >= n) return BAT_FAIL(DSA_E_DEVICE, "internal: bad read %u of %lld", bad, (long long)n);
+            bat_read one{};
+            BAT_HIP(hipMemcpy(&one, rec.p + bad, sizeof(bat_read), hipMemcpyDeviceToHost));
+            return BAT_FAIL(DSA_E_ARG, "%s", read_fault(one, (long long)bad, r->bytes_len).c_str());
+        }
+    }
     hipLaunchKernelGGL(k_reads_keys, dim3(grid_of(n)), dim3(BLOCK), 0, st, (const bat_read*)rec.p, n, key.p, idx.p);
     // stable: of equal keys the last given stays last
     BAT_HIP(hiphost::cub_run(tmp, [&](void* w, size_t& wb) {
@@ -290,6 +330,27 @@ int reads_build(bat_reads* r, const uint8_t* bytes, const bat_read* reads, int64
     BAT_HIP(hipStreamSynchronize(st));
     BAT_HIP(hipGetLastError());
     r->n_unique = U;
+    return DSA_OK;
+}
+
+// the store object around reads_build, after the argument checks
+template <bool DEVICE>
+int reads_create(int device, const uint8_t* bytes, int64_t bytes_len, const bat_read* reads, int64_t n, bat_reads** out)
+{
+    if (hiphost::check_device(device, &g_bat_err)) return DSA_E_DEVICE;
+    BAT_HIP(hipSetDevice(device));
+    bat_reads* r = new bat_reads();
+    r->device = device;
+    r->bytes_len = bytes_len;
+    int rc = DSA_OK;
+    if (r->st.create(hipStreamNonBlocking) != hipSuccess) rc = BAT_FAIL(DSA_E_DEVICE, "cannot create a stream");
+    if (rc == DSA_OK) rc = reads_build<DEVICE>(r, bytes, reads, n);
+    if (rc != DSA_OK) {
+        (void)hipStreamSynchronize(r->st);
+        delete r;
+        return rc;
+    }
+    *out = r;
     return DSA_OK;
 }
 
@@ -433,28 +494,20 @@ int bat_reads_create(int device, const uint8_t* bytes, int64_t bytes_len, const 
     if (n > (int64_t)INT32_MAX) return BAT_FAIL(DSA_E_LIMIT, "more than 2^31 - 1 reads in one store");
     if ((n && !reads) || (bytes_len && !bytes)) return BAT_FAIL(DSA_E_ARG, "bat_reads_create: null pointer with non-zero size");
     for (int64_t k = 0; k < n; ++k) {
-        const bat_read& r = reads[k];
-        if (r.fragment < 0) return BAT_FAIL(DSA_E_ARG, "read %lld: fragment %d is outside [0, 2^31)", (long long)k, r.fragment);
-        if (r.read_end != 0 && r.read_end != 1) return BAT_FAIL(DSA_E_ARG, "read %lld: read_end %d is not 0 or 1", (long long)k, r.read_end);
-        if (r.len < 0) return BAT_FAIL(DSA_E_ARG, "read %lld: negative length %d", (long long)k, r.len);
-        if (r.off < 0 || r.off > bytes_len || (int64_t)r.len > bytes_len - r.off)
-            return BAT_FAIL(DSA_E_ARG, "read %lld: bytes %lld + %d are outside the %lld given", (long long)k, (long long)r.off, r.len, (long long)bytes_len);
+        const std::string fault = read_fault(reads[k], (long long)k, bytes_len);
+        if (!fault.empty()) return BAT_FAIL(DSA_E_ARG, "%s", fault.c_str());
     }
-    if (hiphost::check_device(device, &g_bat_err)) return DSA_E_DEVICE;
-    BAT_HIP(hipSetDevice(device));
-    bat_reads* r = new bat_reads();
-    r->device = device;
-    r->bytes_len = bytes_len;
-    int rc = DSA_OK;
-    if (r->st.create(hipStreamNonBlocking) != hipSuccess) rc = BAT_FAIL(DSA_E_DEVICE, "cannot create a stream");
-    if (rc == DSA_OK) rc = reads_build(r, bytes, reads, n);
-    if (rc != DSA_OK) {
-        (void)hipStreamSynchronize(r->st);
-        delete r;
-        return rc;
-    }
-    *out = r;
-    return DSA_OK;
+    return reads_create<false>(device, bytes, bytes_len, reads, n, out);
+}
+
+int bat_reads_create_device(int device, const void* bytes_device, int64_t bytes_len, const void* reads_device, int64_t n, bat_reads** out)
+{
+    if (!out) return BAT_FAIL(DSA_E_ARG, "bat_reads_create_device: no output");
+    *out = nullptr;
+    if (n < 0 || bytes_len < 0) return BAT_FAIL(DSA_E_ARG, "negative size (%lld reads, %lld bytes)", (long long)n, (long long)bytes_len);
+    if (n > (int64_t)INT32_MAX) return BAT_FAIL(DSA_E_LIMIT, "more than 2^31 - 1 reads in one store");
+    if ((n && !reads_device) || (bytes_len && !bytes_device)) return BAT_FAIL(DSA_E_ARG, "bat_reads_create_device: null pointer with non-zero size");
+    return reads_create<true>(device, static_cast<const uint8_t*>(bytes_device), bytes_len, static_cast<const bat_read*>(reads_device), n, out);
 }
 
 void bat_reads_destroy(bat_reads* r)

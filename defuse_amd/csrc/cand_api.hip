@@ -27,6 +27,7 @@
 #include "../../include/defuse_bat.h"      // cand_enumerate_device, cand_records_device
 #include "../../include/defuse_cand.h"
 #include "../../include/defuse_dsa.h"
+#include "../../include/defuse_text.h"     // cand_enumerate_resident
 #include "hip_host.hpp"
 
 namespace {
@@ -142,6 +143,18 @@ __global__ void k_cand_hits(TabView t, const cand_alignment* __restrict__ al, in
         }
     }
     if (!WRITE) cnt[k] = c;
+}
+
+// check_alignments for alignments that are on the device.  bad[0]: the lowest index with a strand or read end outside 0 / 1;
+// bad[1]: the lowest with fragment < 0 that overlaps something (cnt from k_cand_hits<false>) - one that overlaps nothing
+// is never cast by the reference either (tools/SplitAlignment.cpp:281 is inside the loop over the overlapping ids).
+__global__ void k_cand_check(const cand_alignment* __restrict__ al, const u64* __restrict__ cnt, int64_t n, uint32_t* __restrict__ bad)
+{
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const cand_alignment a = al[k];
+    if ((a.strand != 0 && a.strand != 1) || (a.read_end != 0 && a.read_end != 1)) atomicMin(&bad[0], (uint32_t)k);
+    if (a.fragment < 0 && cnt[k] != 0) atomicMin(&bad[1], (uint32_t)k);
 }
 
 __device__ inline int hit_id(u64 key) { return (int)((unsigned)key ^ 0x80000000u); }
@@ -268,6 +281,7 @@ struct cand_session {
     DeviceBuffer<uint32_t, GrowSize> flag, pos, rank, rank_sorted, keep_v, keep_s, kpos, fkey, fkey_sorted, idx, idx_sorted;
     DeviceBuffer<cand_record, GrowSize> rec, rec_sorted;
     DeviceBuffer<uint8_t, GrowSize> tmp;
+    DeviceBuffer<uint32_t> bad;                  // cand_enumerate_resident: k_cand_check's two indices
     // the records of the latest cand_enumerate_device (in rec or rec_sorted), until the next call on the session
     const cand_record* resident = nullptr;
     int64_t n_resident = 0;
@@ -439,13 +453,15 @@ void cand_session_destroy(cand_session* s)
 namespace {
 
 // cand_enumerate (RESIDENT = false: the records go to `out` if they fit cap) and cand_enumerate_device (true: they stay in
-// the session's buffer, nothing is downloaded and no capacity is asked for)
-template <bool RESIDENT>
+// the session's buffer, nothing is downloaded and no capacity is asked for).  DEVICE_SRC (cand_enumerate_resident): the
+// alignments are in device memory of the session's GPU, a kernel checks them and *first_bad receives what it found.
+template <bool RESIDENT, bool DEVICE_SRC = false>
 int enumerate(cand_session* s, const cand_alignment* alignments, int64_t n, int32_t order, cand_record* out, int64_t cap, int64_t* n_out,
-              cand_timing* timing)
+              cand_timing* timing, int64_t* first_bad = nullptr)
 {
     if (!n_out) return CAND_FAIL(DSA_E_ARG, "cand_enumerate: no n_out");
     *n_out = 0;
+    if (first_bad) *first_bad = -1;
     if (s) {
         s->resident = nullptr;
         s->n_resident = 0;
@@ -455,7 +471,8 @@ int enumerate(cand_session* s, const cand_alignment* alignments, int64_t n, int3
     if (n && !alignments) return CAND_FAIL(DSA_E_ARG, "cand_enumerate: no alignments");
     if (order != CAND_ORDER_VISIT && order != CAND_ORDER_FUSION) return CAND_FAIL(DSA_E_ARG, "order %d is neither CAND_ORDER_VISIT nor CAND_ORDER_FUSION", order);
     if (cap < 0 || (cap && !out)) return CAND_FAIL(DSA_E_ARG, "cand_enumerate: capacity %lld without a buffer", (long long)cap);
-    if (const int rc = check_alignments(alignments, n)) return rc;
+    if (!DEVICE_SRC)
+        if (const int rc = check_alignments(alignments, n)) return rc;
     if (!s) return CAND_FAIL(DSA_E_ARG, "cand_enumerate: no session");
 
     if (timing) *timing = cand_timing{0, 0, 0, 0, n, 0, 0, 0};
@@ -471,18 +488,30 @@ int enumerate(cand_session* s, const cand_alignment* alignments, int64_t n, int3
     CAND_HIP(s->off.reserve((size_t)n));
     CAND_HIP(s->key.reserve(1));
     CAND_HIP(hipEventRecord(s->ev[0], st));
-    CAND_HIP(hipMemcpyAsync(s->al.p, alignments, (size_t)n * sizeof(cand_alignment), hipMemcpyHostToDevice, st));
+    CAND_HIP(hipMemcpyAsync(s->al.p, alignments, (size_t)n * sizeof(cand_alignment), DEVICE_SRC ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     CAND_HIP(hipEventRecord(s->ev[1], st));
 
     // (1) raw hits
     hipLaunchKernelGGL(k_cand_hits<false>, dim3(gn), dim3(BLOCK), 0, st, t->view(), s->al.p, n, s->cnt.p, (const u64*)s->off.p, s->key.p, (int64_t)0);
     CAND_HIP(hiphost::cub_run(s->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, s->cnt.p, s->off.p, (int)n, st); }));
+    uint32_t bad[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    if (DEVICE_SRC) {
+        CAND_HIP(s->bad.reserve(2));
+        CAND_HIP(hipMemcpyAsync(s->bad.p, bad, sizeof bad, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_cand_check, dim3(gn), dim3(BLOCK), 0, st, (const cand_alignment*)s->al.p, (const u64*)s->cnt.p, n, s->bad.p);
+        CAND_HIP(hipMemcpyAsync(bad, s->bad.p, sizeof bad, hipMemcpyDeviceToHost, st));
+    }
     {
         u64 last[2] = {0, 0};
         CAND_HIP(hipMemcpyAsync(&last[0], s->off.p + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
         CAND_HIP(hipMemcpyAsync(&last[1], s->cnt.p + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, st));
         CAND_HIP(hipStreamSynchronize(st));
         CAND_HIP(hipGetLastError());
+        if (DEVICE_SRC && (int64_t)bad[0] < n) return CAND_FAIL(DSA_E_ARG, "alignment %u: strand or read_end is not 0 or 1", bad[0]);
+        if (DEVICE_SRC && (int64_t)bad[1] < n) {
+            if (first_bad) *first_bad = (int64_t)bad[1];
+            return CAND_FAIL(DSA_E_ARG, "alignment %u: its fragment is outside [0, 2^31) and it overlaps a mate region", bad[1]);
+        }
         if (last[0] + last[1] > (u64)INT32_MAX)
             return CAND_FAIL(DSA_E_LIMIT, "%llu overlaps in one call: more than 2^31 - 1, give fewer alignments per call", last[0] + last[1]);
         H = (int64_t)(last[0] + last[1]);
@@ -593,6 +622,12 @@ int cand_enumerate(cand_session* s, const cand_alignment* alignments, int64_t n,
 int cand_enumerate_device(cand_session* s, const cand_alignment* alignments, int64_t n, int32_t order, int64_t* n_out, cand_timing* timing)
 {
     return enumerate<true>(s, alignments, n, order, nullptr, 0, n_out, timing);
+}
+
+int cand_enumerate_resident(cand_session* s, const void* alignments_device, int64_t n, int32_t order, int64_t* n_out, int64_t* first_bad, cand_timing* timing)
+{
+    if (!first_bad) return CAND_FAIL(DSA_E_ARG, "cand_enumerate_resident: no first_bad");
+    return enumerate<true, true>(s, static_cast<const cand_alignment*>(alignments_device), n, order, nullptr, 0, n_out, timing, first_bad);
 }
 
 int cand_records_device(const cand_session* s, const void** dev, int64_t* n)
