@@ -300,6 +300,13 @@ __device__ __forceinline__ uint4 load_group(const uint4* p)
     const u32x4 v = *reinterpret_cast<const u32x4*>(p);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
+// All vector-memory operations of the wave issued so far are complete (s_waitcnt vmcnt(0) alone, gfx9 encoding).  In front of
+// a loop that prefetches one row group ahead: the compiler places its waits by the union of what may be pending on every
+// edge into the loop header.  With the loads of row group 0 still pending on the entry edge, it puts a wait for them behind
+// the prefetch loads at the top of every iteration, counted for the path on which the boundary load is not issued, so that
+// in the steady state every row group waits for the row bytes it has just asked for.  With nothing pending on entry the only
+// wait left in a row group is the one at its bottom, where the prefetched operands are taken over.
+__device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 // ---------------------------------------------------------------------------------------------
 // K0: byte -> packed code, code16 = byte<<8.
@@ -892,17 +899,25 @@ __device__ __forceinline__ void combine_wg(
 // Replay bookkeeping of one lane: the next kept row of either matrix, the row at which the sweep
 // meets it and the (biased) value its row maximum has there.  Kept rows ascend in a: M1 (row a) meets
 // them in order k = 0.., M2 (row lq-a) in reverse.  The first KCACHE kept rows may come from LDS
-// (kc != nullptr: kc[k * WG_LANES] is kept row k of the pair).
+// (kc[k * WG_LANES] is kept row k of the pair).
 struct HitCursor {
     int k0, k1;
     int row0, row1;        // -1: none left on that side
     uint32_t t0, t1;
     uint64_t valid0, valid1;   // columns of the tile that exist in the reference
 };
+// Two explicit paths: an LDS read that every caller makes (the slot clamped, always there) and, only for k >= KCACHE, a global
+// read that is waited for inside its branch.  As `k < KCACHE ? LDS : global` the two pointers were merged into one and read
+// with a flat load, whose wait (vmcnt(0) and lgkmcnt(0)) every lane with a further kept row paid, the prefetch of the
+// replay's next row group with it.
 __device__ __forceinline__ KeptRow kept_row(const KeptRow* __restrict__ kr, const uint64_t* kc, int k)
 {
-    if (kc != nullptr && k < KCACHE) return __builtin_bit_cast(KeptRow, kc[k * WG_LANES]);
-    return kr[k];
+    KeptRow r = __builtin_bit_cast(KeptRow, kc[(k < KCACHE ? k : KCACHE - 1) * WG_LANES]);
+    if (k >= KCACHE) {
+        r = kr[k];
+        wait_loads();
+    }
+    return r;
 }
 __device__ __forceinline__ void cursor_next0(HitCursor& hc, const KeptRow* __restrict__ kr, const uint64_t* kc, int n_kept, bool has0)
 {
@@ -1095,20 +1110,26 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
     const uint4 bias4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint32_t bprev = BIAS2;
     const int ngq = (Rw >> 2) + 1;
-    auto boundary = [&](int gq) -> uint4 {
-        uint4 x0 = bias4, x1 = bias4;                      // the stops are the lane's own: one 16-byte load per side under its mask
+    // The boundary words of a row group come as loaded, one 16-byte load per side under the lane's own stop, and are merged
+    // (M1's field of the one, M2's of the other) only where the next iteration uses them: masking them here would wait
+    // for each load where it is issued, and the row codes' prefetch with it.
+    auto fetch = [&](int gq, uint4& x0, uint4& x1) {
+        x0 = bias4;
+        x1 = bias4;
         if (gq < stop0) x0 = load_group(bi0 + (int64_t)gq * WAVE);
         if (gq < stop1) x1 = load_group(bi1 + (int64_t)gq * WAVE);
-        return make_uint4((x0.x & 0xFFFFu) | (x1.x & 0xFFFF0000u), (x0.y & 0xFFFFu) | (x1.y & 0xFFFF0000u),
-                          (x0.z & 0xFFFFu) | (x1.z & 0xFFFF0000u), (x0.w & 0xFFFFu) | (x1.w & 0xFFFF0000u));
     };
-    uint4 rc_n = rows4[0];
-    uint4 b_n = boundary(0);
+    auto merged = [](uint32_t lo, uint32_t hi) -> uint32_t { return (lo & 0xFFFFu) | (hi & 0xFFFF0000u); };
+    uint4 rc_n = load_group(rows4);
+    uint4 x0_n, x1_n;
+    fetch(0, x0_n, x1_n);
+    wait_loads();                                        // nothing pending on the loop's entry edge (see wait_loads)
     for (int gq = 0; gq < ngq; ++gq) {
-        const uint4 rc = rc_n, b = b_n;
+        const uint4 rc = rc_n;
+        const uint4 b = make_uint4(merged(x0_n.x, x1_n.x), merged(x0_n.y, x1_n.y), merged(x0_n.z, x1_n.z), merged(x0_n.w, x1_n.w));
         const int gn = gq + 1 < ngq ? gq + 1 : gq;
-        rc_n = rows4[(int64_t)gn * WAVE];
-        b_n = boundary(gn);
+        rc_n = load_group(rows4 + (int64_t)gn * WAVE);
+        fetch(gn, x0_n, x1_n);
         const uint32_t rcv[4] = {rc.x, rc.y, rc.z, rc.w}, bv[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
         for (int sidx = 0; sidx < 4; ++sidx) {
@@ -1179,15 +1200,18 @@ __device__ __forceinline__ int sweep_tile_generic(const uint32_t (&r)[WT], const
     const uint4 bias4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint32_t bprev = BIAS2;
     const int ngq = (lq >> 2) + 1;
-    uint4 rc_n = rows4[0];
-    uint4 b_n = first ? bias4 : bi4[0];                     // every tile stores at least its first row group
+    uint4 rc_n = load_group(rows4);
+    uint4 b_n = bias4;
+    if (!first) b_n = load_group(bi4);                      // uniform; every tile stores at least its first row group
+    wait_loads();                                           // nothing pending on the loop's entry edge (see wait_loads)
     last_bnd = 0;
     int gq = 0;
     for (; gq < ngq; ++gq) {
         const uint4 rc = rc_n, b = b_n;
         const int gn = gq + 1 < ngq ? gq + 1 : gq;          // prefetch the next four rows' operands
-        rc_n = rows4[(int64_t)gn * WAVE];
-        b_n = (!first && gn < stop_prev) ? bi4[(int64_t)gn * WAVE] : bias4;   // past the left tile's stop: dead, V = 0
+        rc_n = load_group(rows4 + (int64_t)gn * WAVE);
+        b_n = bias4;                                        // past the left tile's stop: dead, V = 0
+        if (gn < stop_prev) b_n = load_group(bi4 + (int64_t)gn * WAVE);   // uniform (the first tile has stop_prev = 0)
         const uint32_t rcv[4] = {rc.x, rc.y, rc.z, rc.w}, bv[4] = {b.x, b.y, b.z, b.w};
         uint32_t cmv[4] = {BIAS2, BIAS2, BIAS2, BIAS2}, bov[4] = {BIAS2, BIAS2, BIAS2, BIAS2};
         bool alive = false;
@@ -1420,7 +1444,9 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
     uint32_t bprev = BIAS2;
     const int ngq = (lq_max >> 2) + 1;
     uint32_t rc_n = rows1[0];                               // four rows' bytes: table row / classes
-    uint4 b_n = first_tile ? bias4 : bi4[0];                // every tile stores at least its first row group
+    uint4 b_n = bias4;
+    if (!first_tile) b_n = load_group(bi4);                 // uniform; every tile stores at least its first row group
+    wait_loads();                                           // nothing pending on the loop's entry edge (see wait_loads)
     last_bnd = 0;
     int gq = 0;
     int n_gap_groups = 0;
@@ -1555,6 +1581,7 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
                 bprev = in_prev;
                 b_n = bb;
                 rc_n = rows1[(int64_t)g2 * WAVE];
+                wait_loads();                                       // this back edge, too, carries nothing pending
                 gq = g2 - 1;
             }
         }
