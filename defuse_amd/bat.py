@@ -3,10 +3,11 @@ import ctypes
 
 import numpy as np
 
-from . import cand, dsa
-from .dsa import load_library
+from . import cand, capi, dsa
+from .capi import ptr as _ptr
+from .dsa import load_library      # noqa: F401  (bat.load_library() is what callers of _bind pass)
 
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 
 
 class Read(ctypes.Structure):
@@ -35,58 +36,40 @@ EXPORTS = ["bat_reads_create", "bat_reads_destroy", "bat_windows_create", "bat_w
            "cand_enumerate_device", "cand_records_device"]
 
 
-class BatError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("bat error %d: %s" % (code, msg))
-        self.code = code
+class BatError(capi.ApiError):
+    prefix = "bat"
+
+
+p, i32, i64, cint = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "bat_reads_create": (cint, [cint, p, i64, p, i64, ctypes.POINTER(p)]),
+    "bat_reads_destroy": (None, [p]),
+    "bat_windows_create": (cint, [cint, p, i64, p, i32, ctypes.POINTER(p)]),
+    "bat_windows_destroy": (None, [p]),
+    "bat_batch_create": (cint, [cint, ctypes.POINTER(p)]),
+    "bat_batch_destroy": (None, [p]),
+    "bat_assemble": (cint, [p, p, p, i64, p]),
+    "bat_assemble_device": (cint, [p, p, p, i64, p]),
+    "bat_batch_view": (cint, [p, ctypes.POINTER(View)]),
+    "bat_batch_fetch": (cint, [p, p, i64, p, i64, p, i64, p, i64]),
+    "bat_get_timing": (cint, [p, ctypes.POINTER(BatTiming)]),
+    "bat_last_error": (ctypes.c_char_p, []),
+    "cand_enumerate_device": (cint, [p, p, i64, i32, ctypes.POINTER(i64), ctypes.POINTER(cand.CandTiming)]),
+    "cand_records_device": (cint, [p, ctypes.POINTER(p), ctypes.POINTER(i64)]),
+}
 
 
 def _bind(lib):
-    p, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.bat_reads_create.argtypes = [ctypes.c_int, p, i64, p, i64, ctypes.POINTER(p)]
-    lib.bat_reads_destroy.argtypes = [p]
-    lib.bat_reads_destroy.restype = None
-    lib.bat_windows_create.argtypes = [ctypes.c_int, p, i64, p, i32, ctypes.POINTER(p)]
-    lib.bat_windows_destroy.argtypes = [p]
-    lib.bat_windows_destroy.restype = None
-    lib.bat_batch_create.argtypes = [ctypes.c_int, ctypes.POINTER(p)]
-    lib.bat_batch_destroy.argtypes = [p]
-    lib.bat_batch_destroy.restype = None
-    lib.bat_assemble.argtypes = [p, p, p, i64, p]
-    lib.bat_assemble_device.argtypes = [p, p, p, i64, p]
-    lib.bat_batch_view.argtypes = [p, ctypes.POINTER(View)]
-    lib.bat_batch_fetch.argtypes = [p, p, i64, p, i64, p, i64, p, i64]
-    lib.bat_get_timing.argtypes = [p, ctypes.POINTER(BatTiming)]
-    lib.bat_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_bat.h, and of defuse_cand.h before it, bound."""
+    return _bind(cand.lib())
 
 
 def _fail(lib, what, rc):
     raise BatError(rc, "%s: %s" % (what, lib.bat_last_error().decode()))
-
-
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
-
-
-class _Handle:
-    _destroy = None
-
-    handle = None
-
-    def close(self):
-        if self.handle:
-            getattr(self._lib, self._destroy)(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def pack_reads(reads):
@@ -112,15 +95,14 @@ def pack_windows(windows):
     return np.frombuffer(b"".join(bytes(w0) + bytes(w1) for w0, w1 in windows.values()), dtype=np.uint8), fus
 
 
-class Reads(_Handle):
+class Reads(capi.Owned):
     """The reads of a run on one device (bat_reads_create): `data` uint8, `recs` READ_DTYPE, or see from_dict."""
     _destroy = "bat_reads_destroy"
 
     def __init__(self, data, recs, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         data = np.ascontiguousarray(data, dtype=np.uint8)
         recs = np.ascontiguousarray(recs, dtype=READ_DTYPE)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.bat_reads_create(device, _ptr(data), data.size, _ptr(recs), len(recs), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "bat_reads_create", rc)
@@ -130,15 +112,14 @@ class Reads(_Handle):
         return cls(*pack_reads(reads), device=device)
 
 
-class Windows(_Handle):
+class Windows(capi.Owned):
     """Both windows of every task on one device (bat_windows_create): `ref_bytes` uint8, `fusions` dsa.FUSION_DTYPE."""
     _destroy = "bat_windows_destroy"
 
     def __init__(self, ref_bytes, fusions, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         ref_bytes = np.ascontiguousarray(ref_bytes, dtype=np.uint8)
         fusions = np.ascontiguousarray(fusions, dtype=dsa.FUSION_DTYPE)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.bat_windows_create(device, _ptr(ref_bytes), ref_bytes.size, _ptr(fusions), len(fusions), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "bat_windows_create", rc)
@@ -148,13 +129,12 @@ class Windows(_Handle):
         return cls(*pack_windows(windows), device=device)
 
 
-class Batch(_Handle):
+class Batch(capi.Owned):
     """The device buffers of an assembled batch (bat_batch_create), reused call after call."""
     _destroy = "bat_batch_destroy"
 
     def __init__(self, device=0):
-        self._lib = _bind(load_library())
-        self.handle = ctypes.c_void_p()
+        super().__init__(lib())
         rc = self._lib.bat_batch_create(device, ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "bat_batch_create", rc)

@@ -3,12 +3,13 @@ import ctypes
 
 import numpy as np
 
-from . import dsa
+from . import capi, dsa
+from .capi import ptr as _ptr
 from .dsa import load_library
 
 BIN_SPACING = 2000              # CAND_BIN_SPACING
 ORDER_VISIT, ORDER_FUSION = 0, 1
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 
 
 class Region(ctypes.Structure):
@@ -42,44 +43,42 @@ EXPORTS = ["cand_cluster_id", "cand_table_create", "cand_table_destroy", "cand_s
            "cand_session_destroy", "cand_enumerate", "cand_last_error"]
 
 
-class CandError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("cand error %d: %s" % (code, msg))
-        self.code = code
+class CandError(capi.ApiError):
+    prefix = "cand"
+
+
+p, i32, i64, cint = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "cand_cluster_id": (cint, [i64, i32, ctypes.POINTER(i32)]),
+    "cand_table_create": (cint, [cint, p, i64, i32, ctypes.POINTER(p)]),
+    "cand_table_destroy": (None, [p]),
+    "cand_session_create": (cint, [p, ctypes.POINTER(p)]),
+    "cand_session_reset": (cint, [p]),
+    "cand_session_destroy": (None, [p]),
+    "cand_enumerate": (cint, [p, p, i64, i32, p, i64, ctypes.POINTER(i64), ctypes.POINTER(CandTiming)]),
+    "cand_last_error": (ctypes.c_char_p, []),
+}
 
 
 def _bind(lib):
-    p, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.cand_cluster_id.argtypes = [i64, i32, ctypes.POINTER(i32)]
-    lib.cand_table_create.argtypes = [ctypes.c_int, p, i64, i32, ctypes.POINTER(p)]
-    lib.cand_table_destroy.argtypes = [p]
-    lib.cand_table_destroy.restype = None
-    lib.cand_session_create.argtypes = [p, ctypes.POINTER(p)]
-    lib.cand_session_reset.argtypes = [p]
-    lib.cand_session_destroy.argtypes = [p]
-    lib.cand_session_destroy.restype = None
-    lib.cand_enumerate.argtypes = [p, p, i64, i32, p, i64, ctypes.POINTER(i64), ctypes.POINTER(CandTiming)]
-    lib.cand_enumerate_device.argtypes = [p, p, i64, i32, ctypes.POINTER(i64), ctypes.POINTER(CandTiming)]      # (declared in defuse_bat.h)
-    lib.cand_records_device.argtypes = [p, ctypes.POINTER(p), ctypes.POINTER(i64)]
-    lib.cand_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_cand.h bound."""
+    return _bind(load_library())
 
 
 def _fail(lib, what, rc):
     raise CandError(rc, "%s: %s" % (what, lib.cand_last_error().decode()))
 
 
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
-
-
 def cluster_id(fusion_id, cluster_end):
     """ClusterID.id of (fusion, cluster end) (cand_cluster_id); raises CandError(DSA_E_ARG) for a fusion id outside [0, 2^31)."""
-    lib = _bind(load_library())
     out = ctypes.c_int32()
-    rc = lib.cand_cluster_id(int(fusion_id), int(cluster_end), ctypes.byref(out))
+    rc = lib().cand_cluster_id(int(fusion_id), int(cluster_end), ctypes.byref(out))
     if rc != 0:
-        _fail(lib, "cand_cluster_id", rc)
+        _fail(lib(), "cand_cluster_id", rc)
     return out.value
 
 
@@ -99,13 +98,13 @@ def alignments(rows):
     return np.array([tuple(r) for r in rows], dtype=ALIGNMENT_DTYPE).reshape(-1)
 
 
-class Table:
+class Table(capi.Owned):
     """The binned mate regions on one device (cand_table_create); close() or a with-block frees them, after the sessions."""
+    _destroy = "cand_table_destroy"
 
     def __init__(self, regs, bin_spacing=BIN_SPACING, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         r = np.ascontiguousarray(regs, dtype=REGION_DTYPE)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.cand_table_create(device, _ptr(r), len(r), int(bin_spacing), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "cand_table_create", rc)
@@ -113,28 +112,14 @@ class Table:
     def session(self):
         return Session(self)
 
-    def close(self):
-        if self.handle:
-            self._lib.cand_table_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
-
-class Session:
+class Session(capi.Owned):
     """What one DoAlignment run has kept so far (cand_session_create)."""
+    _destroy = "cand_session_destroy"
 
     def __init__(self, table):
-        self._lib = table._lib
+        super().__init__(table._lib)
         self._table = table                                  # the table outlives its sessions
-        self.handle = ctypes.c_void_p()
         rc = self._lib.cand_session_create(table.handle, ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "cand_session_create", rc)
@@ -175,6 +160,8 @@ class Session:
     def enumerate_device(self, als, order=ORDER_VISIT):
         """cand_enumerate_device: the kept candidates stay in the session's device buffer.  Returns (device pointer, count)
         from cand_records_device, valid until the next call on this session; the timing is in self.timing."""
+        from . import bat                                    # (bat imports this module: its header declares the two device twins)
+        bat.lib()
         a = np.ascontiguousarray(als, dtype=ALIGNMENT_DTYPE)
         n = ctypes.c_int64()
         rc = self._lib.cand_enumerate_device(self.handle, _ptr(a), len(a), order, ctypes.byref(n), ctypes.byref(self.timing))
@@ -190,20 +177,6 @@ class Session:
         rc = self._lib.cand_session_reset(self.handle)
         if rc != 0:
             _fail(self._lib, "cand_session_reset", rc)
-
-    def close(self):
-        if self.handle:
-            self._lib.cand_session_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 _COMPLEMENT = np.arange(256, dtype=np.uint8)

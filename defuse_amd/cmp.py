@@ -4,9 +4,11 @@ import ctypes
 
 import numpy as np
 
-from .dsa import load_library
+from . import capi, mpe
+from .capi import ptr as _ptr
+from .mpe import MpeParams, MpeTiming      # noqa: F401  (cmp.MpeParams is what callers of cluster_batch build)
 
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 
 i32, i64, u16, u32, f32, f64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 
@@ -43,17 +45,9 @@ class ProblemsDevice(ctypes.Structure):
                 ("n_problems", i64), ("n_mate_pairs", i64), ("device", i32), ("pad_", i32)]
 
 
-class MpeParams(ctypes.Structure):
-    _fields_ = [("fragment_mean", f64), ("fragment_stddev", f64), ("min_probability", f64), ("min_cluster_size", i32), ("pad_", i32)]
-
-
-class MpeTiming(ctypes.Structure):
-    _fields_ = [("kernel_ms", f32), ("n_problems", i32), ("n_mate_pairs", i64), ("em_iterations", i64), ("n_failed", i32), ("n_wave_problems", i32)]
-
-
 STRUCTS = {"cmp_record": Record, "cmp_packed": Packed, "cmp_stats": Stats, "cmp_problem_counts": ProblemCounts, "cmp_pair": Pair, "cmp_row": Row,
            "cmp_problems_device": ProblemsDevice}
-MPE_STRUCTS = {"mpe_params": MpeParams, "mpe_timing": MpeTiming}
+MPE_STRUCTS = mpe.STRUCTS
 RECORD_DTYPE = np.dtype([("fragment", "<i4"), ("start", "<i4"), ("end", "<i4"), ("meta", "<u4")])
 PACKED_DTYPE = np.dtype([("fragment", "<i4"), ("read_end", "<i4"), ("rel_start", "<u2"), ("rel_end", "<u2")])
 PAIR_DTYPE = np.dtype([("first", "<i4"), ("second", "<i4")])
@@ -66,77 +60,54 @@ assert (RECORD_DTYPE.itemsize, PACKED_DTYPE.itemsize, PAIR_DTYPE.itemsize, ROW_D
 EXPORTS = ["cmp_bin_create", "cmp_bin_destroy", "cmp_bin_reserve", "cmp_bin_upload_records", "cmp_bin_upload_fragments", "cmp_bin_run",
            "cmp_bin_fetch", "cmp_bin_fetch_part", "cmp_last_error", "cmp_problems_create", "cmp_problems_destroy", "cmp_problems_build",
            "cmp_problems_build_lists", "cmp_problems_fetch", "cmp_problems_view", "cmp_problems_select", "cmp_problems_rows"]
-MPE_EXPORTS = ["mpe_cluster_batch", "mpe_cluster_batch_device", "mpe_cluster_batch_sharded", "mpe_last_error"]
+MPE_EXPORTS = mpe.EXPORTS
 
 
-class CmpError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("cmp error %d: %s" % (code, msg))
-        self.code = code
+class CmpError(capi.ApiError):
+    prefix = "cmp"
+
+
+P, cint = ctypes.POINTER, ctypes.c_int
+PROTOTYPES = {
+    "cmp_bin_create": (cint, [P(vp), cint]),
+    "cmp_bin_destroy": (None, [vp]),
+    "cmp_bin_reserve": (cint, [vp, i64, i64]),
+    "cmp_bin_upload_records": (cint, [vp, vp, i64, i64]),
+    "cmp_bin_upload_fragments": (cint, [vp, vp, i64, i64]),
+    "cmp_bin_run": (cint, [vp, i32, P(Stats)]),
+    "cmp_bin_fetch": (cint, [vp, vp, vp, vp, vp, vp]),
+    "cmp_bin_fetch_part": (cint, [vp, cint, i64, i64, vp]),
+    "cmp_last_error": (ctypes.c_char_p, []),
+    "cmp_problems_create": (cint, [P(vp), cint]),
+    "cmp_problems_destroy": (None, [vp]),
+    "cmp_problems_build": (cint, [vp, vp, i32, i32, f64, P(ProblemCounts)]),
+    "cmp_problems_build_lists": (cint, [vp, vp, vp, vp, vp, vp, i64, i32, i32, f64, P(ProblemCounts)]),
+    "cmp_problems_fetch": (cint, [vp] + [vp] * 8),
+    "cmp_problems_view": (cint, [vp, P(ProblemsDevice)]),
+    "cmp_problems_select": (cint, [vp, i64, i64, vp, vp, i32, P(i64)]),
+    "cmp_problems_rows": (cint, [vp, vp, i64, P(i64)]),
+}
 
 
 def _bind(lib):
-    P = ctypes.POINTER
-    lib.cmp_bin_create.argtypes = [P(vp), ctypes.c_int]
-    lib.cmp_bin_destroy.argtypes = [vp]
-    lib.cmp_bin_destroy.restype = None
-    lib.cmp_bin_reserve.argtypes = [vp, i64, i64]
-    lib.cmp_bin_upload_records.argtypes = [vp, vp, i64, i64]
-    lib.cmp_bin_upload_fragments.argtypes = [vp, vp, i64, i64]
-    lib.cmp_bin_run.argtypes = [vp, i32, P(Stats)]
-    lib.cmp_bin_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.cmp_bin_fetch_part.argtypes = [vp, ctypes.c_int, i64, i64, vp]
-    lib.cmp_last_error.restype = ctypes.c_char_p
-    lib.cmp_problems_create.argtypes = [P(vp), ctypes.c_int]
-    lib.cmp_problems_destroy.argtypes = [vp]
-    lib.cmp_problems_destroy.restype = None
-    lib.cmp_problems_build.argtypes = [vp, vp, i32, i32, f64, P(ProblemCounts)]
-    lib.cmp_problems_build_lists.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, f64, P(ProblemCounts)]
-    lib.cmp_problems_fetch.argtypes = [vp] + [vp] * 8
-    lib.cmp_problems_view.argtypes = [vp, P(ProblemsDevice)]
-    lib.cmp_problems_select.argtypes = [vp, i64, i64, vp, vp, i32, P(i64)]
-    lib.cmp_problems_rows.argtypes = [vp, vp, i64, P(i64)]
-    batch = [ctypes.c_int, P(MpeParams), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, P(MpeTiming)]
-    lib.mpe_cluster_batch.argtypes = batch
-    lib.mpe_cluster_batch_device.argtypes = batch
-    lib.mpe_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_cmp.h and defuse_mpe.h bound."""
+    return _bind(mpe.lib())
 
 
 def _fail(lib, what, rc):
     raise CmpError(rc, "%s: %s" % (what, lib.cmp_last_error().decode()))
 
 
-def _ptr(a):
-    return a.ctypes.data if a is not None and len(a) else None
-
-
-class _Handle:
-    _destroy = None
-    handle = None
-
-    def close(self):
-        if self.handle:
-            getattr(self._lib, self._destroy)(self.handle)
-            self.handle = vp()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
-
-class Binner(_Handle):
+class Binner(capi.Owned):
     """cmp_bin_*: records (RECORD_DTYPE) and fragment starts (uint32, one more entry = the number of records) -> bin pairs."""
     _destroy = "cmp_bin_destroy"
 
     def __init__(self, device=0):
-        self._lib = _bind(load_library())
-        self.handle = vp()
+        super().__init__(lib())
         rc = self._lib.cmp_bin_create(ctypes.byref(self.handle), device)
         if rc != 0:
             _fail(self._lib, "cmp_bin_create", rc)
@@ -172,13 +143,12 @@ class Binner(_Handle):
 ARRAYS = ("prob_off", "x", "y", "u", "to_xo", "to_yo", "pairs", "bin_pair")
 
 
-class Problems(_Handle):
+class Problems(capi.Owned):
     """cmp_problems_*: the EM problems of the bin pairs, built and kept on the device."""
     _destroy = "cmp_problems_destroy"
 
     def __init__(self, device=0):
-        self._lib = _bind(load_library())
-        self.handle = vp()
+        super().__init__(lib())
         self.device = device
         rc = self._lib.cmp_problems_create(ctypes.byref(self.handle), device)
         if rc != 0:
@@ -256,7 +226,7 @@ class Problems(_Handle):
 def cluster_batch(params, prob_off, x, y, u, to_xo, to_yo, device=0, on_device=None):
     """mpe_cluster_batch of host arrays -> (n_clusters, member, status).  With on_device = (x, y, u, to_xo, to_yo, member) device
     pointers, mpe_cluster_batch_device: member stays on the device and None is returned in its place."""
-    lib = _bind(load_library())
+    bound = lib()
     prob_off = np.ascontiguousarray(prob_off, dtype=np.int64)
     n = len(prob_off) - 1
     ncl, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
@@ -264,12 +234,12 @@ def cluster_batch(params, prob_off, x, y, u, to_xo, to_yo, device=0, on_device=N
     if on_device is None:
         member = np.zeros(int(prob_off[-1]), dtype=np.uint16)
         arrs = [np.ascontiguousarray(a, dtype=d) for a, d in ((x, np.float64), (y, np.float64), (u, np.float64), (to_xo, np.int32), (to_yo, np.int32))]
-        rc = lib.mpe_cluster_batch(device, ctypes.byref(params), prob_off.ctypes.data, n, *[a.ctypes.data for a in arrs], ncl.ctypes.data,
-                                   member.ctypes.data, status.ctypes.data, ctypes.byref(t))
+        rc = bound.mpe_cluster_batch(device, ctypes.byref(params), prob_off.ctypes.data, n, *[a.ctypes.data for a in arrs], ncl.ctypes.data,
+                                     member.ctypes.data, status.ctypes.data, ctypes.byref(t))
     else:
         member = None
-        rc = lib.mpe_cluster_batch_device(device, ctypes.byref(params), prob_off.ctypes.data, n, *[vp(a) for a in on_device[:5]], ncl.ctypes.data,
-                                          vp(on_device[5]), status.ctypes.data, ctypes.byref(t))
+        rc = bound.mpe_cluster_batch_device(device, ctypes.byref(params), prob_off.ctypes.data, n, *[vp(a) for a in on_device[:5]], ncl.ctypes.data,
+                                            vp(on_device[5]), status.ctypes.data, ctypes.byref(t))
     if rc != 0:
-        raise CmpError(rc, "mpe_cluster_batch: " + lib.mpe_last_error().decode())
+        raise CmpError(rc, "mpe_cluster_batch: " + bound.mpe_last_error().decode())
     return ncl, member, status

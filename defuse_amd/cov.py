@@ -3,7 +3,9 @@ import ctypes
 
 import numpy as np
 
-from .dsa import DSA_E_CAPACITY, load_library
+from . import capi
+from .capi import E_CAPACITY as DSA_E_CAPACITY
+from .dsa import load_library
 
 FRAGMENT_DTYPE = np.dtype([("ref", "<i4"), ("start", "<i4", (2,)), ("end", "<i4", (2,))])
 assert FRAGMENT_DTYPE.itemsize == 20
@@ -14,19 +16,22 @@ class CovTiming(ctypes.Structure):
                 ("n_split_samples", ctypes.c_int64)]
 
 
-class CovError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("cov error %d: %s" % (code, msg))
-        self.code = code
+class CovError(capi.ApiError):
+    prefix = "cov"
 
 
-def _lib():
-    lib = load_library()
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.cov_sample_batch.argtypes = [ctypes.c_int, vp, i32, vp, vp, i64, i32, i32, vp, vp, i64, ctypes.POINTER(i64),
-                                     vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(CovTiming)]
-    lib.cov_last_error.restype = ctypes.c_char_p
-    return lib
+vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+PROTOTYPES = {
+    "cov_sample_batch": (ctypes.c_int, [ctypes.c_int, vp, i32, vp, vp, i64, i32, i32, vp, vp, i64, ctypes.POINTER(i64),
+                                        vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(CovTiming)]),
+    "cov_last_error": (ctypes.c_char_p, []),
+}
+EXPORTS = list(PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_cov.h bound."""
+    return capi.bind(load_library(), PROTOTYPES)
 
 
 def fragments_array(fragments):
@@ -40,16 +45,15 @@ def fragments_array(fragments):
 def sample_batch_raw(sample_off, sample_pos, fragments, trim, anchor, length_idx, length_val, split_idx, split_pos, split_min, device=0):
     """One call of cov_sample_batch into the caller's arrays (their sizes are the capacities): (return code, n_length,
     n_split, timing)."""
-    lib = _lib()
     off = np.ascontiguousarray(sample_off, dtype=np.int64)
     pos = np.ascontiguousarray(sample_pos, dtype=np.int32)
     fr = np.ascontiguousarray(fragments, dtype=FRAGMENT_DTYPE)
     assert len(length_idx) == len(length_val) and len(split_idx) == len(split_pos) == len(split_min)
-    ptr = lambda a: a.ctypes.data if len(a) else None
+    ptr = capi.ptr
     nl, ns, t = ctypes.c_int64(-1), ctypes.c_int64(-1), CovTiming()
-    rc = lib.cov_sample_batch(device, off.ctypes.data, len(off) - 1, ptr(pos), ptr(fr), len(fr), trim, anchor,
-                              ptr(length_idx), ptr(length_val), len(length_idx), ctypes.byref(nl),
-                              ptr(split_idx), ptr(split_pos), ptr(split_min), len(split_idx), ctypes.byref(ns), ctypes.byref(t))
+    rc = lib().cov_sample_batch(device, off.ctypes.data, len(off) - 1, ptr(pos), ptr(fr), len(fr), trim, anchor,
+                                ptr(length_idx), ptr(length_val), len(length_idx), ctypes.byref(nl),
+                                ptr(split_idx), ptr(split_pos), ptr(split_min), len(split_idx), ctypes.byref(ns), ctypes.byref(t))
     return rc, nl.value, ns.value, t
 
 
@@ -64,5 +68,5 @@ def sample_batch(sample_off, sample_pos, fragments, trim, anchor, device=0):
         out = room(nl, ns)
         rc, nl, ns, t = sample_batch_raw(sample_off, sample_pos, fragments, trim, anchor, *out, device=device)
     if rc != 0:
-        raise CovError(rc, _lib().cov_last_error().decode())
+        raise CovError(rc, lib().cov_last_error().decode())
     return out + (t,)

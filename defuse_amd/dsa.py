@@ -8,6 +8,8 @@ import os
 
 import numpy as np
 
+from . import capi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DEFUSE_DSA_LIB") or os.path.join(_HERE, "libdefuse_dsa.so")
 
@@ -25,9 +27,7 @@ EXPORTS = ["dsa_create", "dsa_destroy", "dsa_get_limits", "dsa_tile_cols_for", "
            "dsa_host_alloc", "dsa_host_free", "dsa_host_register", "dsa_host_unregister"]
 
 PLAN_NO_REORDER, PLAN_NO_RANK, PLAN_NO_TIGHTEN, PLAN_NO_LPT = 1, 2, 4, 8
-DSA_E_CAPACITY = -1
-DSA_E_ARG = -3
-DSA_E_BUSY = -5
+DSA_E_CAPACITY, DSA_E_ARG, DSA_E_BUSY = capi.E_CAPACITY, capi.E_ARG, capi.E_BUSY
 
 
 class Limits(ctypes.Structure):
@@ -48,11 +48,52 @@ class KernelCounts(ctypes.Structure):
                 ("long_pairs", ctypes.c_int64), ("generic_tasks", ctypes.c_int64)]
 
 
-class DsaError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("dsa error %d: %s" % (code, msg))
-        self.code = code
+class DsaError(capi.ApiError):
+    prefix = "dsa"
 
+
+STRUCTS = {"dsa_limits": Limits, "dsa_timing": Timing, "dsa_kernel_counts": KernelCounts}
+
+P, vp, i32, i64, cint, cstr = ctypes.POINTER, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int, ctypes.c_char_p
+batch = [vp, vp, i64, vp, i32, vp, i64, vp, i64]
+# every function include/defuse_dsa.h declares: name -> (restype, argtypes)
+PROTOTYPES = {
+    "dsa_create": (cint, [P(vp), cint]),
+    "dsa_destroy": (None, [vp]),
+    "dsa_get_limits": (cint, [vp, P(Limits)]),
+    "dsa_tile_cols_for": (cint, [i32]),
+    "dsa_tile_cols_in_use": (cint, [vp]),
+    "dsa_last_error": (cstr, [vp]),
+    "dsa_version": (cstr, []),
+    "dsa_build_flags": (cstr, []),
+    "dsa_device_count": (cint, []),
+    "dsa_pick_device": (cint, []),
+    "dsa_pick_device_among": (cint, [cint]),
+    "dsa_set_plan_options": (cint, [vp, ctypes.c_uint]),
+    "dsa_set_scratch_budget": (cint, [vp, i64]),
+    "dsa_share_scratch": (cint, [vp, vp]),
+    "dsa_align_batch": (cint, batch + [vp, i64, P(i64)]),
+    "dsa_upload": (cint, batch),
+    "dsa_upload_device": (cint, batch),
+    "dsa_plan": (cint, [vp]),
+    "dsa_run": (cint, [vp, P(i64)]),
+    "dsa_download": (cint, [vp, vp, i64, P(i64)]),
+    "dsa_copy_records_device": (cint, [vp, vp, i64, P(i64)]),
+    "dsa_get_timing": (cint, [vp, P(Timing)]),
+    "dsa_get_kernel_counts": (cint, [vp, P(KernelCounts)]),
+    "dsa_set_stream": (cint, [vp, vp]),
+    "dsa_synchronize": (cint, [vp]),
+    "dsa_stream_create": (cint, [P(vp), cint, cint]),
+    "dsa_stream_destroy": (None, [vp]),
+    "dsa_stream_submit": (cint, [vp] + batch[1:] + [vp, i64]),
+    "dsa_stream_collect": (cint, [vp, P(i64)]),
+    "dsa_stream_recollect": (cint, [vp, vp, i64, P(i64)]),
+    "dsa_stream_last_error": (cstr, [vp]),
+    "dsa_host_alloc": (vp, [ctypes.c_size_t]),
+    "dsa_host_free": (None, [vp]),
+    "dsa_host_register": (cint, [vp, ctypes.c_size_t]),
+    "dsa_host_unregister": (cint, [vp]),
+}
 
 _lib = None
 
@@ -63,50 +104,11 @@ def load_library():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("%s missing: run `python -m defuse_amd.build`" % LIB_PATH)
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.dsa_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-        lib.dsa_destroy.argtypes = [vp]
-        lib.dsa_destroy.restype = None
-        lib.dsa_get_limits.argtypes = [vp, ctypes.POINTER(Limits)]
-        lib.dsa_tile_cols_for.argtypes = [i32]
-        lib.dsa_tile_cols_in_use.argtypes = [vp]
-        lib.dsa_last_error.argtypes = [vp]
-        lib.dsa_last_error.restype = ctypes.c_char_p
-        lib.dsa_version.restype = ctypes.c_char_p
-        lib.dsa_build_flags.restype = ctypes.c_char_p
-        batch = [vp, vp, i64, vp, i32, vp, i64, vp, i64]
-        lib.dsa_align_batch.argtypes = batch + [vp, i64, ctypes.POINTER(i64)]
-        lib.dsa_upload.argtypes = batch
-        lib.dsa_upload_device.argtypes = batch
-        lib.dsa_plan.argtypes = [vp]
-        lib.dsa_run.argtypes = [vp, ctypes.POINTER(i64)]
-        lib.dsa_download.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
-        lib.dsa_copy_records_device.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
-        lib.dsa_get_timing.argtypes = [vp, ctypes.POINTER(Timing)]
-        lib.dsa_get_kernel_counts.argtypes = [vp, ctypes.POINTER(KernelCounts)]
-        lib.dsa_set_stream.argtypes = [vp, vp]
-        lib.dsa_synchronize.argtypes = [vp]
-        lib.dsa_set_scratch_budget.argtypes = [vp, i64]
-        lib.dsa_set_plan_options.argtypes = [vp, ctypes.c_uint]
-        lib.dsa_share_scratch.argtypes = [vp, vp]
-        lib.dsa_pick_device_among.argtypes = [ctypes.c_int]
-        lib.dsa_stream_create.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int]
-        lib.dsa_stream_destroy.argtypes = [vp]
-        lib.dsa_stream_destroy.restype = None
-        lib.dsa_stream_submit.argtypes = [vp] + batch[1:] + [vp, i64]
-        lib.dsa_stream_collect.argtypes = [vp, ctypes.POINTER(i64)]
-        lib.dsa_stream_recollect.argtypes = [vp, vp, i64, ctypes.POINTER(i64)]
-        lib.dsa_stream_last_error.argtypes = [vp]
-        lib.dsa_stream_last_error.restype = ctypes.c_char_p
-        lib.dsa_host_alloc.argtypes = [ctypes.c_size_t]
-        lib.dsa_host_alloc.restype = vp
-        lib.dsa_host_free.argtypes = [vp]
-        lib.dsa_host_free.restype = None
-        lib.dsa_host_register.argtypes = [vp, ctypes.c_size_t]
-        lib.dsa_host_unregister.argtypes = [vp]
-        _lib = lib
+        _lib = capi.bind(ctypes.CDLL(LIB_PATH), PROTOTYPES)
     return _lib
+
+
+lib = load_library      # the spelling every binding module has
 
 
 def tile_cols_for(max_window):

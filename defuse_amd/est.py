@@ -3,6 +3,8 @@ import ctypes
 
 import numpy as np
 
+from . import capi
+from .capi import ptr as _ptr
 from .dsa import load_library
 
 PAD = 300                       # EST_ISLAND_PAD
@@ -14,35 +16,40 @@ class EstTiming(ctypes.Structure):
                 ("n_contained", ctypes.c_int64)]
 
 
+p, i64, cint = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "est_catalog_create": (cint, [cint, p, p, p, i64, ctypes.c_int32, ctypes.POINTER(p)]),
+    "est_catalog_islands": (cint, [p, p, p, i64, ctypes.POINTER(i64), p]),
+    "est_catalog_contained": (cint, [p, p, p, p, i64, p, ctypes.POINTER(EstTiming)]),
+    "est_catalog_destroy": (None, [p]),
+    "est_last_error": (ctypes.c_char_p, []),
+}
+EXPORTS = list(PROTOTYPES)
+
+
 def _bind(lib):
-    p = ctypes.c_void_p
-    lib.est_catalog_create.argtypes = [ctypes.c_int, p, p, p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
-    lib.est_catalog_islands.argtypes = [p, p, p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), p]
-    lib.est_catalog_contained.argtypes = [p, p, p, p, ctypes.c_int64, p, ctypes.POINTER(EstTiming)]
-    lib.est_catalog_destroy.argtypes = [p]
-    lib.est_catalog_destroy.restype = None
-    lib.est_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_est.h bound."""
+    return _bind(load_library())
 
 
 def _col(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
-
-
-class Catalog:
+class Catalog(capi.Owned):
     """The islands of EST segments (dense chromosome ids in [0, n_chrom), start, end) on one device
     (est_catalog_create); close() or a with-block frees them."""
+    _destroy = "est_catalog_destroy"
 
     def __init__(self, chrom, start, end, n_chrom, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         c, s, e = _col(chrom), _col(start), _col(end)
         assert len(c) == len(s) == len(e)
         self.n_chrom = int(n_chrom)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.est_catalog_create(device, _ptr(c), _ptr(s), _ptr(e), len(c), self.n_chrom, ctypes.byref(self.handle))
         if rc != 0:
             raise RuntimeError("est_catalog_create failed (%d): %s" % (rc, self._lib.est_last_error().decode()))
@@ -70,20 +77,6 @@ class Catalog:
         if rc != 0:
             raise RuntimeError("est_catalog_contained failed (%d): %s" % (rc, self._lib.est_last_error().decode()))
         return out, t
-
-    def close(self):
-        if self.handle:
-            self._lib.est_catalog_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def catalog(chrom, start, end, n_chrom, device=0):

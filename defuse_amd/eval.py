@@ -6,10 +6,12 @@ import ctypes
 
 import numpy as np
 
-from .dsa import DSA_E_CAPACITY, RECORD_DTYPE, DsaError, load_library
+from . import capi
+from .capi import ptr as _ptr
+from .dsa import RECORD_DTYPE, DsaError, load_library
 
 NO_SPLIT, HOST_STATS = 1, 2      # EVAL_NO_SPLIT, EVAL_HOST_STATS
-DSA_E_DEVICE, DSA_E_LIMIT = -2, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_LIMIT
 
 GROUP_DTYPE = np.dtype([("fusion_id", "<i4"), ("status", "<i4"), ("first_record", "<i8"), ("n_records", "<i8"),
                         ("best_first", "<i4"), ("best_second", "<i4"), ("best_score", "<i4"), ("pad_", "<i4"),
@@ -33,28 +35,40 @@ class EvalTiming(ctypes.Structure):
                 ("n_flagged", ctypes.c_int64)]
 
 
+STRUCTS = {"eval_group": EvalGroup, "eval_timing": EvalTiming}
+
+p, i64, cint = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+call = [p, p, i64, p, i64, ctypes.POINTER(i64), p, i64, ctypes.POINTER(i64)]
+PROTOTYPES = {
+    "eval_create": (cint, [cint, ctypes.POINTER(p)]),
+    "eval_destroy": (None, [p]),
+    "eval_groups": (cint, call),
+    "eval_groups_device": (cint, call),
+    "eval_get_timing": (cint, [p, ctypes.POINTER(EvalTiming)]),
+    "eval_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _bind(lib):
-    p, i64 = ctypes.c_void_p, ctypes.c_int64
-    lib.eval_create.argtypes = [ctypes.c_int, ctypes.POINTER(p)]
-    lib.eval_destroy.argtypes = [p]
-    lib.eval_destroy.restype = None
-    call = [p, p, i64, p, i64, ctypes.POINTER(i64), p, i64, ctypes.POINTER(i64)]
-    lib.eval_groups.argtypes = call
-    lib.eval_groups_device.argtypes = call
-    lib.eval_get_timing.argtypes = [p, ctypes.POINTER(EvalTiming)]
-    lib.eval_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
 
 
-class Context:
+def lib():
+    """The library with the functions of include/defuse_eval.h bound."""
+    return _bind(load_library())
+
+
+class Context(capi.Owned):
     """One eval_ctx (one device); close() or a with-block frees its device buffers.  No CPU path: raises without a GPU."""
+    _destroy = "eval_destroy"
+    h = property(lambda self: self.handle)      # the older spelling of .handle and ._lib
+    lib = property(lambda self: self._lib)
 
     def __init__(self, device=0):
-        self.lib = _bind(load_library())
-        self.h = ctypes.c_void_p()
-        rc = self.lib.eval_create(int(device), ctypes.byref(self.h))
+        super().__init__(lib())
+        rc = self._lib.eval_create(int(device), ctypes.byref(self.handle))
         if rc != 0:
-            raise DsaError(rc, "eval_create: " + self.lib.eval_last_error().decode())
+            raise DsaError(rc, "eval_create: " + self._lib.eval_last_error().decode())
 
     def _call(self, fn, ptr, n, group_cap=None, kept_cap=None):
         """(groups, kept): a GROUP_DTYPE array and the int64 kept list.  Without capacities the arrays have room for n groups
@@ -66,10 +80,10 @@ class Context:
             group_cap = kept_cap = n
         groups = np.zeros(group_cap, GROUP_DTYPE)
         kept = np.zeros(kept_cap, np.int64)
-        rc = fn(self.h, ptr, n, groups.ctypes.data if group_cap else None, group_cap, ctypes.byref(ng),
+        rc = fn(self.handle, ptr, n, groups.ctypes.data if group_cap else None, group_cap, ctypes.byref(ng),
                 kept.ctypes.data if kept_cap else None, kept_cap, ctypes.byref(nk))
         if rc != 0:
-            e = DsaError(rc, self.lib.eval_last_error().decode())
+            e = DsaError(rc, self._lib.eval_last_error().decode())
             e.n_groups, e.n_kept = ng.value, nk.value
             raise e
         if sized:
@@ -79,32 +93,15 @@ class Context:
     def evaluate(self, records, group_cap=None, kept_cap=None):
         """eval_groups on a structured array with the layout of dsa_record (dsa.RECORD_DTYPE)."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        return self._call(self.lib.eval_groups, records.ctypes.data if len(records) else None, len(records), group_cap, kept_cap)
+        return self._call(self._lib.eval_groups, _ptr(records), len(records), group_cap, kept_cap)
 
     def evaluate_device(self, ptr, n, group_cap=None, kept_cap=None):
         """eval_groups_device: n records at a device pointer (an int, e.g. what dsa.Context.records_to_device filled)."""
-        return self._call(self.lib.eval_groups_device, ctypes.c_void_p(ptr), int(n), group_cap, kept_cap)
+        return self._call(self._lib.eval_groups_device, ctypes.c_void_p(ptr), int(n), group_cap, kept_cap)
 
     def timing(self):
         t = EvalTiming()
-        rc = self.lib.eval_get_timing(self.h, ctypes.byref(t))
+        rc = self._lib.eval_get_timing(self.handle, ctypes.byref(t))
         if rc != 0:
-            raise DsaError(rc, self.lib.eval_last_error().decode())
-        return {name: getattr(t, name) for name, _ in EvalTiming._fields_ if name != "pad_"}
-
-    def close(self):
-        if self.h:
-            self.lib.eval_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            raise DsaError(rc, self._lib.eval_last_error().decode())
+        return capi.as_dict(t)

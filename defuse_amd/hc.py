@@ -3,6 +3,7 @@ import ctypes
 
 import numpy as np
 
+from . import capi
 from .dsa import load_library
 
 
@@ -11,12 +12,22 @@ class HcTiming(ctypes.Structure):
                 ("n_merges", ctypes.c_int32)]
 
 
+vp = ctypes.c_void_p
+PROTOTYPES = {
+    "hc_cluster_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(HcTiming)]),
+    "hc_last_error": (ctypes.c_char_p, []),
+}
+EXPORTS = list(PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_hc.h bound."""
+    return capi.bind(load_library(), PROTOTYPES)
+
+
 def cluster_batch(tables, thresholds, device=0):
     """tables: list of n×n arrays; thresholds: one per table.  Returns (list of cluster lists per table, timing)."""
-    lib = load_library()
-    vp = ctypes.c_void_p
-    lib.hc_cluster_batch.argtypes = [ctypes.c_int, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(HcTiming)]
-    lib.hc_last_error.restype = ctypes.c_char_p
+    bound = lib()
     mats = [np.ascontiguousarray(t, dtype=np.float64).reshape(len(t), len(t)) if len(t) else np.zeros((0, 0)) for t in tables]
     n_items = np.array([len(m) for m in mats], dtype=np.int32)
     dist_off = np.zeros(len(mats), dtype=np.int64)
@@ -29,10 +40,10 @@ def cluster_batch(tables, thresholds, device=0):
     cluster_of = np.zeros(max(total, 1), dtype=np.int32)
     n_clusters = np.zeros(max(len(mats), 1), dtype=np.int32)
     t = HcTiming()
-    rc = lib.hc_cluster_batch(device, len(mats), n_items.ctypes.data, dist_off.ctypes.data, flat.ctypes.data if flat.size else None,
-                              thr.ctypes.data, members.ctypes.data, cluster_of.ctypes.data, n_clusters.ctypes.data, ctypes.byref(t))
+    rc = bound.hc_cluster_batch(device, len(mats), n_items.ctypes.data, dist_off.ctypes.data, flat.ctypes.data if flat.size else None,
+                                thr.ctypes.data, members.ctypes.data, cluster_of.ctypes.data, n_clusters.ctypes.data, ctypes.byref(t))
     if rc != 0:
-        raise RuntimeError("hc_cluster_batch failed (%d): %s" % (rc, lib.hc_last_error().decode()))
+        raise RuntimeError("hc_cluster_batch failed (%d): %s" % (rc, bound.hc_last_error().decode()))
     out, base = [], 0
     for p, n in enumerate(n_items):
         cl = [[] for _ in range(n_clusters[p])]

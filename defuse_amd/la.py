@@ -3,6 +3,7 @@ import ctypes
 
 import numpy as np
 
+from . import capi
 from .dsa import load_library
 
 LA_ITEM = np.dtype([("ref_off", np.int64), ("seq_off", np.int64), ("ref_len", np.int32), ("seq_len", np.int32)])
@@ -14,13 +15,27 @@ class LaTiming(ctypes.Structure):
                 ("cells", ctypes.c_int64)]
 
 
+p, i32, i64, cint = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "la_align_batch": (cint, [cint, i32, i32, i32, p, i64, p, i64, p, ctypes.POINTER(LaTiming)]),
+    "la_align_batch_min": (cint, [cint, i32, i32, i32, p, i64, p, i64, p, p, ctypes.POINTER(LaTiming)]),
+    "la_genome_create": (cint, [cint, p, i64, ctypes.POINTER(p)]),
+    "la_genome_destroy": (None, [p]),
+    "la_align_windows_min": (cint, [p, i32, i32, i32, p, i64, p, i64, p, p, ctypes.POINTER(LaTiming)]),
+    "la_last_error": (ctypes.c_char_p, []),
+}
+EXPORTS = list(PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_la.h bound."""
+    return capi.bind(load_library(), PROTOTYPES)
+
+
 def align_batch(pairs, match, mismatch, gap, device=0, min_score=None):
     """pairs: list of (reference bytes, sequence bytes).  Returns (int32 scores, timing).  With min_score (one
     int per pair) a score below its minimum is only guaranteed to be below it (la_align_batch_min)."""
-    lib = load_library()
-    lib.la_align_batch_min.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(LaTiming)]
-    lib.la_last_error.restype = ctypes.c_char_p
+    bound = lib()
     items = np.zeros(len(pairs), dtype=LA_ITEM)
     chunks, off = [], 0
     for k, (r, s) in enumerate(pairs):
@@ -31,11 +46,11 @@ def align_batch(pairs, match, mismatch, gap, device=0, min_score=None):
     scores = np.zeros(len(pairs), dtype=np.int32)
     t = LaTiming()
     need = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.int32)
-    rc = lib.la_align_batch_min(device, match, mismatch, gap, pool.ctypes.data, off, items.ctypes.data if len(pairs) else None,
-                                len(pairs), need.ctypes.data if need is not None and len(pairs) else None,
-                                scores.ctypes.data if len(pairs) else None, ctypes.byref(t))
+    rc = bound.la_align_batch_min(device, match, mismatch, gap, pool.ctypes.data, off, items.ctypes.data if len(pairs) else None,
+                                  len(pairs), need.ctypes.data if need is not None and len(pairs) else None,
+                                  scores.ctypes.data if len(pairs) else None, ctypes.byref(t))
     if rc != 0:
-        raise RuntimeError("la_align_batch_min failed (%d): %s" % (rc, lib.la_last_error().decode()))
+        raise RuntimeError("la_align_batch_min failed (%d): %s" % (rc, bound.la_last_error().decode()))
     return scores, t
 
 
@@ -43,41 +58,17 @@ LA_WINDOW = np.dtype([("slice_off", np.int64), ("seq_off", np.int64), ("slice_le
                       ("pad_right", np.int32), ("seq_len", np.int32), ("revcomp", np.int32), ("pad_", np.int32)])
 
 
-def _bind_windows(lib):
-    lib.la_genome_create.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]
-    lib.la_genome_destroy.argtypes = [ctypes.c_void_p]
-    lib.la_genome_destroy.restype = None
-    lib.la_align_windows_min.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(LaTiming)]
-    lib.la_last_error.restype = ctypes.c_char_p
-    return lib
-
-
-class Genome:
+class Genome(capi.Owned):
     """Contig bytes in HBM (la_genome_create); close() or a with-block frees them."""
+    _destroy = "la_genome_destroy"
 
     def __init__(self, data, device=0):
-        self._lib = _bind_windows(load_library())
+        super().__init__(lib())
         buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
         self.len = len(buf) - 1
-        self.handle = ctypes.c_void_p()
         rc = self._lib.la_genome_create(device, buf.ctypes.data, self.len, ctypes.byref(self.handle))
         if rc != 0:
             raise RuntimeError("la_genome_create failed (%d): %s" % (rc, self._lib.la_last_error().decode()))
-
-    def close(self):
-        if self.handle:
-            self._lib.la_genome_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
 
 def genome(data, device=0):
@@ -89,7 +80,7 @@ def align_windows(gen, reads, windows, match, mismatch, gap, min_score=None):
     """la_align_windows_min.  reads: list of byte strings; windows: one (read index, slice_off, slice_len, pad_left,
     pad_right, revcomp) per pair, or an LA_WINDOW array whose seq_off / seq_len index the concatenated reads.
     Returns (int32 scores, timing)."""
-    lib = gen._lib
+    bound = gen._lib
     pool = b"".join(bytes(r) for r in reads)
     if isinstance(windows, np.ndarray) and windows.dtype == LA_WINDOW:
         items = np.ascontiguousarray(windows)
@@ -103,10 +94,10 @@ def align_windows(gen, reads, windows, match, mismatch, gap, min_score=None):
     scores = np.zeros(n, dtype=np.int32)
     t = LaTiming()
     need = None if min_score is None else np.ascontiguousarray(min_score, dtype=np.int32)
-    rc = lib.la_align_windows_min(gen.handle, match, mismatch, gap, buf.ctypes.data, len(pool), items.ctypes.data if n else None, n,
-                                  need.ctypes.data if need is not None and n else None, scores.ctypes.data if n else None, ctypes.byref(t))
+    rc = bound.la_align_windows_min(gen.handle, match, mismatch, gap, buf.ctypes.data, len(pool), items.ctypes.data if n else None, n,
+                                    need.ctypes.data if need is not None and n else None, scores.ctypes.data if n else None, ctypes.byref(t))
     if rc != 0:
-        raise RuntimeError("la_align_windows_min failed (%d): %s" % (rc, lib.la_last_error().decode()))
+        raise RuntimeError("la_align_windows_min failed (%d): %s" % (rc, bound.la_last_error().decode()))
     return scores, t
 
 

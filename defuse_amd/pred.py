@@ -4,10 +4,12 @@ import ctypes
 
 import numpy as np
 
+from . import capi
 from . import eval as ev
+from .capi import ptr as _ptr
 from .dsa import load_library
 
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 NO_TASK, OUT_OF_WINDOW = 4, 8      # PRED_NO_TASK, PRED_OUT_OF_WINDOW
 
 TASK_DTYPE = np.dtype([("fusion_id", "<i4"), ("pad_", "<i4"), ("seq_start", "<i4", (2,)), ("seq_len", "<i4", (2,)),
@@ -48,35 +50,36 @@ EXPORTS = ["pred_tasks_create", "pred_tasks_destroy", "pred_create", "pred_destr
            "pred_fetch", "pred_get_timing", "pred_last_error"]
 
 
-class PredError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("pred error %d: %s" % (code, msg))
-        self.code = code
+class PredError(capi.ApiError):
+    prefix = "pred"
+
+
+p, i64, cint = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "pred_tasks_create": (cint, [cint, p, p, i64, p, i64, ctypes.POINTER(p)]),
+    "pred_tasks_destroy": (None, [p]),
+    "pred_create": (cint, [cint, ctypes.POINTER(p)]),
+    "pred_destroy": (None, [p]),
+    "pred_predict": (cint, [p, p, p, i64]),
+    "pred_predict_resident": (cint, [p, p, p]),
+    "pred_view": (cint, [p, ctypes.POINTER(View)]),
+    "pred_fetch": (cint, [p, p, i64, p, i64]),
+    "pred_get_timing": (cint, [p, ctypes.POINTER(PredTiming)]),
+    "pred_last_error": (ctypes.c_char_p, []),
+}
 
 
 def _bind(lib):
-    p, i64 = ctypes.c_void_p, ctypes.c_int64
-    lib.pred_tasks_create.argtypes = [ctypes.c_int, p, p, i64, p, i64, ctypes.POINTER(p)]
-    lib.pred_tasks_destroy.argtypes = [p]
-    lib.pred_tasks_destroy.restype = None
-    lib.pred_create.argtypes = [ctypes.c_int, ctypes.POINTER(p)]
-    lib.pred_destroy.argtypes = [p]
-    lib.pred_destroy.restype = None
-    lib.pred_predict.argtypes = [p, p, p, i64]
-    lib.pred_predict_resident.argtypes = [p, p, p]
-    lib.pred_view.argtypes = [p, ctypes.POINTER(View)]
-    lib.pred_fetch.argtypes = [p, p, i64, p, i64]
-    lib.pred_get_timing.argtypes = [p, ctypes.POINTER(PredTiming)]
-    lib.pred_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_pred.h bound."""
+    return _bind(load_library())
 
 
 def _fail(lib, what, rc):
     raise PredError(rc, "%s: %s" % (what, lib.pred_last_error().decode()))
-
-
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
 
 
 def pack_tasks(tasks):
@@ -94,16 +97,16 @@ def pack_tasks(tasks):
     return np.frombuffer(b"".join(bytes(t.remainder[0]) + bytes(t.remainder[1]) for t in tasks), dtype=np.uint8), recs
 
 
-class Tasks:
+class Tasks(capi.Owned):
     """The tasks of a run on one device (pred_tasks_create) over a bat.Windows, which it keeps alive: `rem_bytes` uint8,
     `recs` TASK_DTYPE, or see from_oracle."""
+    _destroy = "pred_tasks_destroy"
 
     def __init__(self, windows, rem_bytes, recs, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         self.windows = windows
         rem_bytes = np.ascontiguousarray(rem_bytes, dtype=np.uint8)
         recs = np.ascontiguousarray(recs, dtype=TASK_DTYPE)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.pred_tasks_create(device, windows.handle, _ptr(rem_bytes), rem_bytes.size, _ptr(recs), len(recs), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "pred_tasks_create", rc)
@@ -112,29 +115,15 @@ class Tasks:
     def from_oracle(cls, windows, tasks, device=0):
         return cls(windows, *pack_tasks(tasks), device=device)
 
-    def close(self):
-        if self.handle:
-            self._lib.pred_tasks_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
-
-
-class Context:
+class Context(capi.Owned):
     """One pred_ctx (one device): the output buffers of the predictions, reused call after call.  `tasks` is the Tasks the
     predictions use unless a call names another."""
+    _destroy = "pred_destroy"
 
     def __init__(self, tasks=None, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         self.tasks = tasks
-        self.handle = ctypes.c_void_p()
         rc = self._lib.pred_create(int(device), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "pred_create", rc)
@@ -149,7 +138,7 @@ class Context:
 
     def predict_resident(self, eval_ctx, tasks=None):
         """pred_predict_resident on the groups an eval.Context left on the device; returns the view."""
-        rc = self._lib.pred_predict_resident(self.handle, (tasks or self.tasks).handle, eval_ctx.h)
+        rc = self._lib.pred_predict_resident(self.handle, (tasks or self.tasks).handle, eval_ctx.handle)
         if rc != 0:
             _fail(self._lib, "pred_predict_resident", rc)
         return self.view()
@@ -176,7 +165,7 @@ class Context:
         rc = self._lib.pred_get_timing(self.handle, ctypes.byref(t))
         if rc != 0:
             _fail(self._lib, "pred_get_timing", rc)
-        return {name: getattr(t, name) for name, _ in PredTiming._fields_ if name != "pad_"}
+        return capi.as_dict(t)
 
     @staticmethod
     def format_seq(row, seq_bytes):
@@ -191,20 +180,3 @@ class Context:
         of the two cluster ends."""
         return "".join("%d\t%d\t%s\t%s\t%d\n" % (row["fusion_id"], ce, names[ce], "+" if strands[ce] == 0 else "-", row["break_pos"][ce])
                        for ce in (0, 1))
-
-    def close(self):
-        if self.handle:
-            self._lib.pred_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

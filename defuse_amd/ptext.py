@@ -4,9 +4,11 @@ import ctypes
 
 import numpy as np
 
+from . import capi
+from .capi import ptr as _ptr
 from .dsa import load_library
 
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 HOST_SEQ = 16                      # PTEXT_HOST_SEQ
 G_MAX = 12                         # PTEXT_G_MAX of ptext_shared.hpp: the longest "%g" text
 
@@ -44,35 +46,36 @@ EXPORTS = ["ptext_names_create", "ptext_names_destroy", "ptext_create", "ptext_d
            "ptext_get_timing", "ptext_format_doubles", "ptext_last_error"]
 
 
-class PtextError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("ptext error %d: %s" % (code, msg))
-        self.code = code
+class PtextError(capi.ApiError):
+    prefix = "ptext"
+
+
+p, i64, cint = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "ptext_names_create": (cint, [cint, p, i64, p, i64, p, i64, ctypes.POINTER(p)]),
+    "ptext_names_destroy": (None, [p]),
+    "ptext_create": (cint, [cint, ctypes.POINTER(p)]),
+    "ptext_destroy": (None, [p]),
+    "ptext_format": (cint, [p, p, p]),
+    "ptext_view": (cint, [p, ctypes.POINTER(View)]),
+    "ptext_fetch": (cint, [p, p, i64, p, i64, p, i64]),
+    "ptext_get_timing": (cint, [p, ctypes.POINTER(PtextTiming)]),
+    "ptext_format_doubles": (cint, [cint, p, i64, p, i64, p, ctypes.POINTER(i64)]),
+    "ptext_last_error": (ctypes.c_char_p, []),
+}
 
 
 def _bind(lib):
-    p, i64 = ctypes.c_void_p, ctypes.c_int64
-    lib.ptext_names_create.argtypes = [ctypes.c_int, p, i64, p, i64, p, i64, ctypes.POINTER(p)]
-    lib.ptext_names_destroy.argtypes = [p]
-    lib.ptext_names_destroy.restype = None
-    lib.ptext_create.argtypes = [ctypes.c_int, ctypes.POINTER(p)]
-    lib.ptext_destroy.argtypes = [p]
-    lib.ptext_destroy.restype = None
-    lib.ptext_format.argtypes = [p, p, p]
-    lib.ptext_view.argtypes = [p, ctypes.POINTER(View)]
-    lib.ptext_fetch.argtypes = [p, p, i64, p, i64, p, i64]
-    lib.ptext_get_timing.argtypes = [p, ctypes.POINTER(PtextTiming)]
-    lib.ptext_format_doubles.argtypes = [ctypes.c_int, p, i64, p, i64, p, ctypes.POINTER(i64)]
-    lib.ptext_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_ptext.h bound."""
+    return _bind(load_library())
 
 
 def _fail(lib, what, rc):
     raise PtextError(rc, "%s: %s" % (what, lib.ptext_last_error().decode()))
-
-
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
 
 
 def pack_names(tasks):
@@ -89,16 +92,16 @@ def pack_names(tasks):
     return np.frombuffer(b"".join(index), dtype=np.uint8), off, ends
 
 
-class Names:
+class Names(capi.Owned):
     """The reference names and align strands of a run on one device (ptext_names_create): `name_bytes` uint8, `name_off`
     int64 with one entry more than there are names, `ends` END_DTYPE; or see from_oracle."""
+    _destroy = "ptext_names_destroy"
 
     def __init__(self, name_bytes, name_off, ends, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         name_bytes = np.ascontiguousarray(name_bytes, dtype=np.uint8)
         name_off = np.ascontiguousarray(name_off, dtype=np.int64)
         ends = np.ascontiguousarray(ends, dtype=END_DTYPE)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.ptext_names_create(device, _ptr(name_bytes), name_bytes.size, _ptr(name_off), max(len(name_off) - 1, 0), _ptr(ends), len(ends),
                                           ctypes.byref(self.handle))
         if rc != 0:
@@ -108,32 +111,15 @@ class Names:
     def from_oracle(cls, tasks, device=0):
         return cls(*pack_names(tasks), device=device)
 
-    def close(self):
-        if self.handle:
-            self._lib.ptext_names_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Context:
+class Context(capi.Owned):
     """One ptext_ctx (one device): the two texts and the line table, reused call after call.  `names` is the Names the
     calls use unless one names another."""
+    _destroy = "ptext_destroy"
 
     def __init__(self, names=None, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         self.names = names
-        self.handle = ctypes.c_void_p()
         rc = self._lib.ptext_create(int(device), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "ptext_create", rc)
@@ -168,37 +154,20 @@ class Context:
         rc = self._lib.ptext_get_timing(self.handle, ctypes.byref(t))
         if rc != 0:
             _fail(self._lib, "ptext_get_timing", rc)
-        return {name: getattr(t, name) for name, _ in PtextTiming._fields_}
-
-    def close(self):
-        if self.handle:
-            self._lib.ptext_destroy(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return capi.as_dict(t)
 
 
 def format_doubles(x, device=0, cap=None):
     """ptext_format_doubles: the "%g" text of every double of x as the device prints it, a list of bytes objects (b"" where
     the formatter declines)."""
-    lib = _bind(load_library())
+    bound = lib()
     x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.zeros(max(len(x) * G_MAX if cap is None else int(cap), 1), dtype=np.uint8)
     lens = np.zeros(max(len(x), 1), dtype=np.int32)
     total = ctypes.c_int64()
-    rc = lib.ptext_format_doubles(device, _ptr(x), len(x), out.ctypes.data, len(x) * G_MAX if cap is None else int(cap), lens.ctypes.data, ctypes.byref(total))
+    rc = bound.ptext_format_doubles(device, _ptr(x), len(x), out.ctypes.data, len(x) * G_MAX if cap is None else int(cap), lens.ctypes.data, ctypes.byref(total))
     if rc != 0:
-        e = PtextError(rc, "ptext_format_doubles: " + lib.ptext_last_error().decode())
+        e = PtextError(rc, "ptext_format_doubles: " + bound.ptext_last_error().decode())
         e.bytes = total.value
         raise e
     ends = np.cumsum(lens[:len(x)].astype(np.int64))

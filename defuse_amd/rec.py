@@ -7,9 +7,11 @@ import ctypes
 
 import numpy as np
 
-from .dsa import DSA_E_CAPACITY, RECORD_DTYPE, DsaError, load_library
+from . import capi
+from .capi import ptr as _ptr
+from .dsa import RECORD_DTYPE, DsaError, load_library
 
-DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 FIELDS = RECORD_DTYPE.names[:9]      # the printed fields, in print order (pair_idx is not printed)
 MAX_LINE = 109
 
@@ -23,79 +25,91 @@ class RecTiming(ctypes.Structure):
                 ("n_records", ctypes.c_int64), ("n_sorts", ctypes.c_int64), ("text_bytes", ctypes.c_int64)]
 
 
+STRUCTS = {"rec_timing": RecTiming}
+
+p, i64, cint = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "rec_create": (cint, [cint, ctypes.POINTER(p)]),
+    "rec_destroy": (None, [p]),
+    "rec_clear": (cint, [p]),
+    "rec_append": (cint, [p, p, i64]),
+    "rec_append_device": (cint, [p, p, i64]),
+    "rec_tail": (cint, [p, i64, ctypes.POINTER(p)]),
+    "rec_commit": (cint, [p, i64]),
+    "rec_sort": (cint, [p]),
+    "rec_count": (cint, [p, ctypes.POINTER(i64)]),
+    "rec_records_device": (cint, [p, ctypes.POINTER(p), ctypes.POINTER(i64)]),
+    "rec_download": (cint, [p, p, i64, ctypes.POINTER(i64)]),
+    "rec_text": (cint, [p, p, i64, p, i64, ctypes.POINTER(i64)]),
+    "rec_get_timing": (cint, [p, ctypes.POINTER(RecTiming)]),
+    "rec_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _bind(lib):
-    p, i64 = ctypes.c_void_p, ctypes.c_int64
-    lib.rec_create.argtypes = [ctypes.c_int, ctypes.POINTER(p)]
-    lib.rec_destroy.argtypes = [p]
-    lib.rec_destroy.restype = None
-    lib.rec_clear.argtypes = [p]
-    lib.rec_append.argtypes = [p, p, i64]
-    lib.rec_append_device.argtypes = [p, p, i64]
-    lib.rec_tail.argtypes = [p, i64, ctypes.POINTER(p)]
-    lib.rec_commit.argtypes = [p, i64]
-    lib.rec_sort.argtypes = [p]
-    lib.rec_count.argtypes = [p, ctypes.POINTER(i64)]
-    lib.rec_records_device.argtypes = [p, ctypes.POINTER(p), ctypes.POINTER(i64)]
-    lib.rec_download.argtypes = [p, p, i64, ctypes.POINTER(i64)]
-    lib.rec_text.argtypes = [p, p, i64, p, i64, ctypes.POINTER(i64)]
-    lib.rec_get_timing.argtypes = [p, ctypes.POINTER(RecTiming)]
-    lib.rec_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
 
 
-class Store:
+def lib():
+    """The library with the functions of include/defuse_rec.h bound."""
+    return _bind(load_library())
+
+
+class Store(capi.Owned):
     """One rec_store (one device); close() or a with-block frees its device buffers.  No CPU path: raises without a GPU."""
+    _destroy = "rec_destroy"
+    h = property(lambda self: self.handle)      # the older spelling of .handle and ._lib
+    lib = property(lambda self: self._lib)
 
     def __init__(self, device=0):
-        self.lib = _bind(load_library())
-        self.h = ctypes.c_void_p()
-        rc = self.lib.rec_create(int(device), ctypes.byref(self.h))
+        super().__init__(lib())
+        rc = self._lib.rec_create(int(device), ctypes.byref(self.handle))
         if rc != 0:
-            raise DsaError(rc, "rec_create: " + self.lib.rec_last_error().decode())
+            raise DsaError(rc, "rec_create: " + self._lib.rec_last_error().decode())
 
     def _check(self, rc):
         if rc != 0:
-            raise DsaError(rc, self.lib.rec_last_error().decode())
+            raise DsaError(rc, self._lib.rec_last_error().decode())
 
     def clear(self):
-        self._check(self.lib.rec_clear(self.h))
+        self._check(self._lib.rec_clear(self.handle))
 
     def append(self, records):
         """rec_append of a structured array with the layout of dsa_record (dsa.RECORD_DTYPE)."""
         records = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        self._check(self.lib.rec_append(self.h, records.ctypes.data if len(records) else None, len(records)))
+        self._check(self._lib.rec_append(self.handle, _ptr(records), len(records)))
 
     def append_device(self, ptr, n):
         """rec_append_device: n records at a device pointer (an int) of the store's device, their producer completed."""
-        self._check(self.lib.rec_append_device(self.h, ctypes.c_void_p(ptr), int(n)))
+        self._check(self._lib.rec_append_device(self.handle, ctypes.c_void_p(ptr), int(n)))
 
     def tail(self, room):
         """rec_tail: the device pointer (an int) of room for `room` records behind the last one; commit(n) adds n of them."""
         p = ctypes.c_void_p()
-        self._check(self.lib.rec_tail(self.h, int(room), ctypes.byref(p)))
+        self._check(self._lib.rec_tail(self.handle, int(room), ctypes.byref(p)))
         return p.value
 
     def commit(self, n):
-        self._check(self.lib.rec_commit(self.h, int(n)))
+        self._check(self._lib.rec_commit(self.handle, int(n)))
 
     def sort(self):
-        self._check(self.lib.rec_sort(self.h))
+        self._check(self._lib.rec_sort(self.handle))
 
     def __len__(self):
         n = ctypes.c_int64()
-        self._check(self.lib.rec_count(self.h, ctypes.byref(n)))
+        self._check(self._lib.rec_count(self.handle, ctypes.byref(n)))
         return n.value
 
     def records_device(self):
         """(device pointer as an int, n): what eval.Context.evaluate_device takes."""
         p, n = ctypes.c_void_p(), ctypes.c_int64()
-        self._check(self.lib.rec_records_device(self.h, ctypes.byref(p), ctypes.byref(n)))
+        self._check(self._lib.rec_records_device(self.handle, ctypes.byref(p), ctypes.byref(n)))
         return p.value or 0, n.value
 
     def download(self):
         n = ctypes.c_int64()
         out = np.zeros(len(self), RECORD_DTYPE)
-        self._check(self.lib.rec_download(self.h, out.ctypes.data if len(out) else None, len(out), ctypes.byref(n)))
+        self._check(self._lib.rec_download(self.handle, _ptr(out), len(out), ctypes.byref(n)))
         return out
 
     def text(self, kept=None, cap=None):
@@ -110,31 +124,14 @@ class Store:
         size = m * MAX_LINE if cap is None else int(cap)
         buf = np.empty(max(size, 1), np.uint8)
         got = ctypes.c_int64()
-        rc = self.lib.rec_text(self.h, kp, nk, buf.ctypes.data, size, ctypes.byref(got))
+        rc = self._lib.rec_text(self.handle, kp, nk, buf.ctypes.data, size, ctypes.byref(got))
         if rc != 0:
-            e = DsaError(rc, self.lib.rec_last_error().decode())
+            e = DsaError(rc, self._lib.rec_last_error().decode())
             e.bytes = got.value
             raise e
         return buf[:got.value].tobytes()
 
     def timing(self):
         t = RecTiming()
-        self._check(self.lib.rec_get_timing(self.h, ctypes.byref(t)))
-        return {name: getattr(t, name) for name, _ in RecTiming._fields_ if name != "pad_"}
-
-    def close(self):
-        if self.h:
-            self.lib.rec_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(self._lib.rec_get_timing(self.handle, ctypes.byref(t)))
+        return capi.as_dict(t)

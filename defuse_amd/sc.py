@@ -3,6 +3,7 @@ import ctypes
 
 import numpy as np
 
+from . import capi
 from .dsa import load_library
 
 
@@ -12,22 +13,33 @@ class ScTiming(ctypes.Structure):
                 ("cc_iterations", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+PROTOTYPES = {
+    "sc_cover": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                ctypes.POINTER(ScTiming)]),
+    "sc_last_error": (ctypes.c_char_p, []),
+    "sc_prepare": (ctypes.c_int, [ctypes.c_int]),
+}
+EXPORTS = list(PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_sc.h bound."""
+    return capi.bind(load_library(), PROTOTYPES)
+
+
 def cover(clusters, device=0):
     """clusters: list of lists of fragment indices.  Returns (solution lists, timing)."""
-    lib = load_library()
-    lib.sc_cover.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                             ctypes.c_void_p, ctypes.POINTER(ScTiming)]
-    lib.sc_last_error.restype = ctypes.c_char_p
+    bound = lib()
     off = np.zeros(len(clusters) + 1, dtype=np.int64)
     off[1:] = np.cumsum([len(c) for c in clusters])
     el = np.array([e for c in clusters for e in c], dtype=np.int32)
     max_el = int(el.max()) if len(el) else -1
     owner = np.full(max_el + 1, -1, dtype=np.int32)
     t = ScTiming()
-    rc = lib.sc_cover(device, off.ctypes.data, el.ctypes.data if len(el) else None, len(clusters), max_el,
-                      owner.ctypes.data if len(owner) else None, ctypes.byref(t))
+    rc = bound.sc_cover(device, off.ctypes.data, el.ctypes.data if len(el) else None, len(clusters), max_el,
+                        owner.ctypes.data if len(owner) else None, ctypes.byref(t))
     if rc != 0:
-        raise RuntimeError("sc_cover failed (%d): %s" % (rc, lib.sc_last_error().decode()))
+        raise RuntimeError("sc_cover failed (%d): %s" % (rc, bound.sc_last_error().decode()))
     sol = [[] for _ in clusters]
     for c, lst in enumerate(clusters):
         for e in lst:

@@ -4,10 +4,11 @@ import ctypes
 
 import numpy as np
 
-from . import cand
+from . import cand, capi
+from .capi import ptr as _ptr
 from .dsa import load_library
 
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 NO_SEQUENCE_0, BAD_CHROMOSOME_0, NO_SEQUENCE_1, BAD_CHROMOSOME_1 = 1, 2, 4, 8      # TASK_* status bits
 MAX_COORD, MAX_REGION, MAX_PARAM, MAX_SEQ_LEN, EXON_BIN = 1 << 28, 1 << 24, 1 << 20, 1 << 30, 100000
 
@@ -66,71 +67,47 @@ EXPORTS = ["task_reference_create", "task_reference_destroy", "task_exons_create
            "task_store_windows", "task_store_pred_tasks", "task_store_counts", "task_store_fetch", "task_store_get_timing", "task_last_error"]
 
 
-class TaskError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("task error %d: %s" % (code, msg))
-        self.code = code
+class TaskError(capi.ApiError):
+    prefix = "task"
+
+
+p, cint = ctypes.c_void_p, ctypes.c_int
+PROTOTYPES = {
+    "task_reference_create": (cint, [cint, p, i64, p, i64, ctypes.POINTER(p)]),
+    "task_reference_destroy": (None, [p]),
+    "task_exons_create": (cint, [cint, p, i32, p, i32, p, i64, ctypes.POINTER(p)]),
+    "task_exons_destroy": (None, [p]),
+    "task_store_create": (cint, [p, p, ctypes.POINTER(Params), p, i64, ctypes.POINTER(p)]),
+    "task_store_destroy": (None, [p]),
+    "task_store_windows": (p, [p]),
+    "task_store_pred_tasks": (p, [p]),
+    "task_store_counts": (cint, [p, ctypes.POINTER(Counts)]),
+    "task_store_fetch": (cint, [p, p, i64, p, i64, p, i64, p, i64]),
+    "task_store_get_timing": (cint, [p, ctypes.POINTER(TaskTiming)]),
+    "task_last_error": (ctypes.c_char_p, []),
+}
 
 
 def _bind(lib):
-    p = ctypes.c_void_p
-    lib.task_reference_create.argtypes = [ctypes.c_int, p, i64, p, i64, ctypes.POINTER(p)]
-    lib.task_reference_destroy.argtypes = [p]
-    lib.task_reference_destroy.restype = None
-    lib.task_exons_create.argtypes = [ctypes.c_int, p, i32, p, i32, p, i64, ctypes.POINTER(p)]
-    lib.task_exons_destroy.argtypes = [p]
-    lib.task_exons_destroy.restype = None
-    lib.task_store_create.argtypes = [p, p, ctypes.POINTER(Params), p, i64, ctypes.POINTER(p)]
-    lib.task_store_destroy.argtypes = [p]
-    lib.task_store_destroy.restype = None
-    lib.task_store_windows.argtypes = [p]
-    lib.task_store_windows.restype = p
-    lib.task_store_pred_tasks.argtypes = [p]
-    lib.task_store_pred_tasks.restype = p
-    lib.task_store_counts.argtypes = [p, ctypes.POINTER(Counts)]
-    lib.task_store_fetch.argtypes = [p, p, i64, p, i64, p, i64, p, i64]
-    lib.task_store_get_timing.argtypes = [p, ctypes.POINTER(TaskTiming)]
-    lib.task_last_error.restype = ctypes.c_char_p
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_task.h bound."""
+    return _bind(load_library())
 
 
 def _fail(lib, what, rc):
     raise TaskError(rc, "%s: %s" % (what, lib.task_last_error().decode()))
 
 
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
-
-
-class _Handle:
-    _destroy = None
-    handle = None
-
-    def close(self):
-        if self.handle:
-            getattr(self._lib, self._destroy)(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Reference(_Handle):
+class Reference(capi.Owned):
     """The sequences of a FASTA on one device (task_reference_create): {name: bytes} in the caller's order; .index maps a
     name to its sequence index."""
     _destroy = "task_reference_destroy"
 
     def __init__(self, seqs, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         self.index = {name: k for k, name in enumerate(seqs)}
         recs = np.zeros(len(seqs), dtype=SEQ_DTYPE)
         off = 0
@@ -138,20 +115,19 @@ class Reference(_Handle):
             recs[k] = (off, len(s))
             off += len(s)
         data = np.frombuffer(b"".join(bytes(s) for s in seqs.values()), dtype=np.uint8)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.task_reference_create(device, _ptr(data), data.size, _ptr(recs), len(recs), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "task_reference_create", rc)
 
 
-class Exons(_Handle):
+class Exons(capi.Owned):
     """The exon table on one device (task_exons_create).  `table`: {transcript: (gene, chromosome, strand, [(start, end)])};
     transcripts are numbered in ascending name order, the order of the reference's output.  `names`: the dense reference
     numbering ({name: index}), extended here by every chromosome and every "gene|transcript" it does not have yet."""
     _destroy = "task_exons_destroy"
 
     def __init__(self, table, names, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         self.transcripts = sorted(table)
         self.tindex = {t: k for k, t in enumerate(self.transcripts)}
         self.cindex = {}
@@ -165,7 +141,6 @@ class Exons(_Handle):
             exons.extend(ex)
         chrom_ref = np.array([names[c] for c in self.cindex], dtype=np.int32)
         ex = np.array(exons, dtype=np.int32).reshape(-1, 2).view(EXON_DTYPE).reshape(-1)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.task_exons_create(device, _ptr(chrom_ref), len(chrom_ref), _ptr(tx), len(tx), _ptr(ex), len(ex), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "task_exons_create", rc)
@@ -194,14 +169,13 @@ def pairs_from_regions(regions, reference, exons):
     return out
 
 
-class Store(_Handle):
+class Store(capi.Owned):
     """All tasks of a run on one device (task_store_create).  .windows / .tasks stand where a bat.Windows / pred.Tasks do."""
     _destroy = "task_store_destroy"
 
     def __init__(self, reference, exons, params, pairs):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
-        self.handle = ctypes.c_void_p()
         prm = Params(*[int(v) for v in params])
         rc = self._lib.task_store_create(reference.handle, exons.handle, ctypes.byref(prm), _ptr(pairs), len(pairs), ctypes.byref(self.handle))
         if rc != 0:
@@ -234,4 +208,4 @@ class Store(_Handle):
         rc = self._lib.task_store_get_timing(self.handle, ctypes.byref(t))
         if rc != 0:
             _fail(self._lib, "task_store_get_timing", rc)
-        return {name: getattr(t, name) for name, _ in TaskTiming._fields_}
+        return capi.as_dict(t)

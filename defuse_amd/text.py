@@ -4,10 +4,11 @@ import ctypes
 
 import numpy as np
 
-from . import bat, cand
-from .dsa import load_library
+from . import bat, cand, capi
+from .capi import ptr as _ptr
+from .dsa import load_library      # noqa: F401  (text.load_library() is what callers of _bind pass)
 
-DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
+DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = capi.E_CAPACITY, capi.E_DEVICE, capi.E_ARG, capi.E_LIMIT
 MAX_READ_LEN = 1 << 24                                  # TXT_MAX_READ_LEN
 SAM_EMPTY_LINE, SAM_FEW_FIELDS, SAM_BAD_INTEGER, SAM_BAD_QNAME = 2, 3, 4, 5
 FASTQ_BAD_NAME, FASTQ_BAD_END, FASTQ_BAD_FRAGMENT, FASTQ_LONG_READ = 1, 2, 3, 4
@@ -52,42 +53,43 @@ EXPORTS = ["txt_names_create", "txt_names_destroy", "txt_create", "txt_destroy",
            "txt_last_error", "cand_enumerate_resident", "bat_reads_create_device"]
 
 
-class TextError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("text error %d: %s" % (code, msg))
-        self.code = code
+class TextError(capi.ApiError):
+    prefix = "text"
+
+
+p, i32, i64, cint = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+PROTOTYPES = {
+    "txt_names_create": (cint, [cint, p, i64, p, i64, ctypes.POINTER(p)]),
+    "txt_names_destroy": (None, [p]),
+    "txt_create": (cint, [cint, ctypes.POINTER(p)]),
+    "txt_destroy": (None, [p]),
+    "txt_set_max_read_len": (cint, [p, i32]),
+    "txt_parse_sam": (cint, [p, p, p, i64, i32, i32, ctypes.POINTER(SamResult)]),
+    "txt_parse_sam_device": (cint, [p, p, p, i64, i32, i32, ctypes.POINTER(SamResult)]),
+    "txt_sam_view": (cint, [p, ctypes.POINTER(SamView)]),
+    "txt_sam_fetch": (cint, [p, p, i64, p, i64]),
+    "txt_fastq_begin": (cint, [p]),
+    "txt_fastq_add": (cint, [p, p, i64, i32, ctypes.POINTER(FastqResult)]),
+    "txt_fastq_view": (cint, [p, ctypes.POINTER(FastqView)]),
+    "txt_fastq_fetch": (cint, [p, p, i64, p, i64]),
+    "txt_get_timing": (cint, [p, ctypes.POINTER(TxtTiming)]),
+    "txt_last_error": (ctypes.c_char_p, []),
+    "cand_enumerate_resident": (cint, [p, p, i64, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(cand.CandTiming)]),
+    "bat_reads_create_device": (cint, [cint, p, i64, p, i64, ctypes.POINTER(p)]),
+}
 
 
 def _bind(lib):
-    p, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.txt_names_create.argtypes = [ctypes.c_int, p, i64, p, i64, ctypes.POINTER(p)]
-    lib.txt_names_destroy.argtypes = [p]
-    lib.txt_names_destroy.restype = None
-    lib.txt_create.argtypes = [ctypes.c_int, ctypes.POINTER(p)]
-    lib.txt_destroy.argtypes = [p]
-    lib.txt_destroy.restype = None
-    lib.txt_set_max_read_len.argtypes = [p, i32]
-    lib.txt_parse_sam.argtypes = [p, p, p, i64, i32, i32, ctypes.POINTER(SamResult)]
-    lib.txt_parse_sam_device.argtypes = [p, p, p, i64, i32, i32, ctypes.POINTER(SamResult)]
-    lib.txt_sam_view.argtypes = [p, ctypes.POINTER(SamView)]
-    lib.txt_sam_fetch.argtypes = [p, p, i64, p, i64]
-    lib.txt_fastq_begin.argtypes = [p]
-    lib.txt_fastq_add.argtypes = [p, p, i64, i32, ctypes.POINTER(FastqResult)]
-    lib.txt_fastq_view.argtypes = [p, ctypes.POINTER(FastqView)]
-    lib.txt_fastq_fetch.argtypes = [p, p, i64, p, i64]
-    lib.txt_get_timing.argtypes = [p, ctypes.POINTER(TxtTiming)]
-    lib.txt_last_error.restype = ctypes.c_char_p
-    lib.cand_enumerate_resident.argtypes = [p, p, i64, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(cand.CandTiming)]
-    lib.bat_reads_create_device.argtypes = [ctypes.c_int, p, i64, p, i64, ctypes.POINTER(p)]
-    return lib
+    return capi.bind(lib, PROTOTYPES)
+
+
+def lib():
+    """The library with the functions of include/defuse_text.h, and of defuse_bat.h and defuse_cand.h before it, bound."""
+    return _bind(bat.lib())
 
 
 def _fail(lib, what, rc):
     raise TextError(rc, "%s: %s" % (what, lib.txt_last_error().decode()))
-
-
-def _ptr(a):
-    return a.ctypes.data if len(a) else None
 
 
 def _text(text):
@@ -105,51 +107,27 @@ def pack_names(names):
     return np.frombuffer(b"".join(names), dtype=np.uint8), off
 
 
-class _Handle:
-    _destroy = None
-    handle = None
-
-    def close(self):
-        if self.handle:
-            getattr(self._lib, self._destroy)(self.handle)
-            self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Names(_Handle):
+class Names(capi.Owned):
     """The reference names of a run on one device (txt_names_create): a sequence of names, index = position, the numbering
     of cand_region.ref."""
     _destroy = "txt_names_destroy"
 
     def __init__(self, names, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         data, off = pack_names(names)
-        self.handle = ctypes.c_void_p()
         rc = self._lib.txt_names_create(device, _ptr(data), data.size, off.ctypes.data, len(off) - 1, ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "txt_names_create", rc)
 
 
-class Context(_Handle):
+class Context(capi.Owned):
     """One txt_ctx (one device): the alignments of the latest SAM parse and the read store of the FASTQ pieces.  `names` is
     the Names the parses use unless one names another."""
     _destroy = "txt_destroy"
 
     def __init__(self, names=None, device=0):
-        self._lib = _bind(load_library())
+        super().__init__(lib())
         self.names = names
-        self.handle = ctypes.c_void_p()
         rc = self._lib.txt_create(int(device), ctypes.byref(self.handle))
         if rc != 0:
             _fail(self._lib, "txt_create", rc)
@@ -238,18 +216,17 @@ class Context(_Handle):
         rc = self._lib.txt_get_timing(self.handle, ctypes.byref(t))
         if rc != 0:
             _fail(self._lib, "txt_get_timing", rc)
-        return {name: getattr(t, name) for name, _ in TxtTiming._fields_}
+        return capi.as_dict(t)
 
 
 def reads_from_device(bytes_ptr, bytes_len, reads_ptr, n, device=0):
     """bat_reads_create_device -> a bat.Reads; raises bat.BatError."""
-    lib = bat._bind(_bind(load_library()))
+    bound = lib()
     r = bat.Reads.__new__(bat.Reads)
-    r._lib = lib
-    r.handle = ctypes.c_void_p()
-    rc = lib.bat_reads_create_device(int(device), ctypes.c_void_p(bytes_ptr), int(bytes_len), ctypes.c_void_p(reads_ptr), int(n), ctypes.byref(r.handle))
+    capi.Owned.__init__(r, bound)
+    rc = bound.bat_reads_create_device(int(device), ctypes.c_void_p(bytes_ptr), int(bytes_len), ctypes.c_void_p(reads_ptr), int(n), ctypes.byref(r.handle))
     if rc != 0:
-        bat._fail(lib, "bat_reads_create_device", rc)
+        bat._fail(bound, "bat_reads_create_device", rc)
     return r
 
 
@@ -257,16 +234,16 @@ def enumerate_resident(session, alignments_ptr, n, order=cand.ORDER_VISIT):
     """cand_enumerate_resident on a cand.Session: n alignments at a device pointer (Context.sam_view).  Returns (device
     pointer, count) of the records as Session.enumerate_device does; a bad alignment raises cand.CandError, whose first_bad
     is the index the call reports (-1: none)."""
-    lib = _bind(session._lib)
+    bound = lib()
     n_out, first_bad = ctypes.c_int64(), ctypes.c_int64()
-    rc = lib.cand_enumerate_resident(session.handle, ctypes.c_void_p(alignments_ptr), int(n), int(order), ctypes.byref(n_out), ctypes.byref(first_bad),
-                                     ctypes.byref(session.timing))
+    rc = bound.cand_enumerate_resident(session.handle, ctypes.c_void_p(alignments_ptr), int(n), int(order), ctypes.byref(n_out), ctypes.byref(first_bad),
+                                       ctypes.byref(session.timing))
     if rc != 0:
-        e = cand.CandError(rc, "cand_enumerate_resident: " + lib.cand_last_error().decode())
+        e = cand.CandError(rc, "cand_enumerate_resident: " + bound.cand_last_error().decode())
         e.first_bad = first_bad.value
         raise e
     dev, m = ctypes.c_void_p(), ctypes.c_int64()
-    rc = lib.cand_records_device(session.handle, ctypes.byref(dev), ctypes.byref(m))
+    rc = bound.cand_records_device(session.handle, ctypes.byref(dev), ctypes.byref(m))
     if rc != 0 or m.value != n_out.value:
-        cand._fail(lib, "cand_records_device", rc)
+        cand._fail(bound, "cand_records_device", rc)
     return dev.value or 0, n_out.value

@@ -25,7 +25,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from defuse_amd import la  # noqa: E402
-from defuse_amd.dsa import load_library  # noqa: E402
 
 RC = np.arange(256, dtype=np.uint8)
 for a, b in zip(b"ACGTacgt", b"TGCAtgca"):
@@ -158,10 +157,7 @@ def main():
             res["sample_mismatches"] = int(bad)
             del lines
         # A/B on the same pairs
-        lib = load_library()
-        la._bind_windows(lib)
-        lib.la_align_batch_min.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(la.LaTiming)]
+        lib = la.lib()
         ab = wins[:a.ab_pairs]
         t = time.time()
         gen = la.genome(genome.tobytes())

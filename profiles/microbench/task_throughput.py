@@ -142,7 +142,7 @@ def main():
     W = make_world(1, a.chrom_mb, a.transcripts, a.fusions, tmp)
     print("problem: %.0f MB of reference, %d sequences, %d exons, %d fusions (%.1f s)" % (W["data"].size / 1e6, len(W["seqs"]), len(W["exons"]), a.fusions,
                                                                                           time.perf_counter() - t0), flush=True)
-    lib = task._bind(dsa.load_library())
+    lib = task.lib()
     err = lambda: lib.task_last_error().decode()
     prm = task.Params(int(PARAMS[0] - 3 * PARAMS[1]), int(PARAMS[0] + 3 * PARAMS[1]), PARAMS[2], PARAMS[3])
     ptr = lambda x: x.ctypes.data

@@ -8,14 +8,14 @@ the host chain."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOKE = os.path.join(ROOT, "tests", "golden", "smoke")
-HEADER = os.path.join(ROOT, "include", "defuse_bat.h")
 E_CAPACITY, E_DEVICE, E_ARG, E_LIMIT = -1, -2, -3, -4
 ODD_BYTES = b"ACGTNacgtn.\x00\xff*"
 LENGTHS = (0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 150)
@@ -114,33 +114,17 @@ def check_both_entries(bat, cand, batch, reads, windows, cands, rdict, wdict):
 
 
 # ---------------------------------------------------------------------------------------------- without a GPU
-def test_bat_struct_layouts_match_header(bat, tmp_path):
-    """sizeof and offsetof of every struct of the header, as a C++ compiler sees them, against the ctypes structs."""
-    lines = []
-    for cname, st in bat.STRUCTS.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    src = tmp_path / "layout.cpp"
-    src.write_text('#include <cstddef>\n#include <cstdio>\n#include "%s"\nint main() { %s }\n' % (HEADER, " ".join(lines)))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["g++", "-std=c++17", "-o", str(exe), str(src)])
-    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(got) == len(bat.STRUCTS)
-    for line, (cname, st) in zip(got, bat.STRUCTS.items()):
-        want = "%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_)
-        assert line == want
+def test_bat_struct_layouts_match_header(bat):
+    """sizeof and offsetof of every struct of the header, as a C++ and a C compiler see them, against the ctypes structs."""
+    sizes, _ = abi.check("defuse_bat.h", bat, r"(?:bat|cand)_[a-z_]+")
+    assert sizes == [24, 64, 48]
     assert (bat.READ_DTYPE.itemsize, ctypes.sizeof(bat.View), ctypes.sizeof(bat.BatTiming)) == (24, 64, 48)
 
 
 def test_library_exports_bat(bat, cand):
     from defuse_amd import dsa
-    lib = ctypes.CDLL(dsa.LIB_PATH)
-    declared = set(re.findall(r"\b((?:bat|cand)_[a-z_]+)\s*\(", open(HEADER).read()))
-    assert declared == set(bat.EXPORTS) and len(declared) == 14
-    for name in declared | {"dsa_upload_device"}:
-        assert getattr(lib, name) is not None
+    assert abi.check_functions("defuse_bat.h", bat, r"(?:bat|cand)_[a-z_]+") == 14
+    assert ctypes.CDLL(dsa.LIB_PATH).dsa_upload_device is not None
     assert "dsa_upload_device" in dsa.EXPORTS
     assert hasattr(dsa.Context, "upload_device") and hasattr(cand.Session, "enumerate_device")
 
@@ -150,7 +134,7 @@ def test_bat_argument_errors_need_no_device(bat, cand):
     (The errors of bat_assemble that need its objects - an unknown fusion_id, the byte totals, two devices - need a device
     to make the objects on: a store cannot be created without one.  They are in the GPU tests below.)"""
     from defuse_amd import dsa
-    lib = cand._bind(bat._bind(bat.load_library()))
+    lib = bat.lib()
     err = lambda: lib.bat_last_error().decode()
     h = ctypes.c_void_p()
     data = np.frombuffer(b"ACGTACGTAC", dtype=np.uint8)

@@ -5,15 +5,14 @@ equality of the candidate tuples (alignment, fusion, fragment, cluster_end, read
 import ctypes
 import functools
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOKE = os.path.join(ROOT, "tests", "golden", "smoke")
-HEADER = os.path.join(ROOT, "include", "defuse_cand.h")
 INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
 E_CAPACITY, E_DEVICE, E_ARG, E_LIMIT = -1, -2, -3, -4
 
@@ -74,39 +73,21 @@ def by_fusion(exp):
 
 
 # ---------------------------------------------------------------------------------------------- CPU
-def test_struct_layouts_match_header(cand, tmp_path):
-    """sizeof and offsetof of every struct of the header, as a C++ compiler sees them, against the ctypes structs."""
-    lines = []
-    for cname, st in cand.STRUCTS.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    src = tmp_path / "layout.cpp"
-    src.write_text('#include <cstddef>\n#include <cstdio>\n#include "%s"\nint main() { %s }\n' % (HEADER, " ".join(lines)))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["g++", "-std=c++17", "-o", str(exe), str(src)])
-    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(got) == len(cand.STRUCTS)
-    for line, (cname, st) in zip(got, cand.STRUCTS.items()):
-        want = "%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_)
-        assert line == want
+def test_struct_layouts_match_header(cand):
+    """sizeof and offsetof of every struct of the header, as a C++ and a C compiler see them, against the ctypes structs."""
+    sizes, _ = abi.check("defuse_cand.h", cand, r"cand_[a-z_]+")
+    assert sizes == [20, 24, 24, 48]
     assert (cand.REGION_DTYPE.itemsize, cand.ALIGNMENT_DTYPE.itemsize, cand.RECORD_DTYPE.itemsize) == (20, 24, 24)
     assert ctypes.sizeof(cand.CandTiming) == 48
 
 
 def test_library_exports_cand(cand):
-    from defuse_amd.dsa import LIB_PATH
-    lib = ctypes.CDLL(LIB_PATH)
-    declared = set(re.findall(r"\b(cand_[a-z_]+)\s*\(", open(HEADER).read()))
-    assert declared == set(cand.EXPORTS) and len(declared) == 8
-    for name in declared:
-        assert getattr(lib, name) is not None
+    assert abi.check_functions("defuse_cand.h", cand, r"cand_[a-z_]+") == 8
 
 
 def test_argument_errors_need_no_device(cand):
     """Every argument error is found before a device is touched: the code is DSA_E_ARG with or without a GPU."""
-    lib = cand._bind(cand.load_library())
+    lib = cand.lib()
     err = lambda: lib.cand_last_error().decode()
     table = ctypes.c_void_p()
     one = cand.regions([(0, 0, 100, 200, 5)])
@@ -150,7 +131,7 @@ def test_argument_errors_need_no_device(cand):
 
 def too_many_entries(cand):
     """Three regions over the whole int range at spacing 1: 3 * 2^32 (region, bin) entries."""
-    lib = cand._bind(cand.load_library())
+    lib = cand.lib()
     table = ctypes.c_void_p()
     regs = cand.regions([(0, 0, INT_MIN, INT_MAX, 1), (0, 1, INT_MIN, INT_MAX, 2), (1, 0, INT_MIN, INT_MAX, 3)])
     rc = lib.cand_table_create(0, regs.ctypes.data, len(regs), 1, ctypes.byref(table))

@@ -7,18 +7,15 @@ the struct layouts.  With a GPU: hand-made lists with one property each, the bin
 from device arrays against the EM from host arrays, the rows against the rule in Python, and the tool both ways."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import abi
 from tests import cmp_cases
 from tests import cmp_problem_cases as pc
 
 ROOT = pc.ROOT
-HEADER = os.path.join(ROOT, "include", "defuse_cmp.h")
-MPE_HEADER = os.path.join(ROOT, "include", "defuse_mpe.h")
 MFR = int(300 + 10 * 30)                # the tool's minFusionRange with -u 300 -s 30
 
 
@@ -55,38 +52,19 @@ def test_checker_equals_the_host_path(tools, tmp_path, seed):
 
 
 def test_library_exports_cmp_problems(cmp):
-    from defuse_amd import dsa
-    lib = ctypes.CDLL(dsa.LIB_PATH)
-    declared = set(re.findall(r"\b(cmp_[a-z_]+)\s*\(", open(HEADER).read()))
-    assert declared == set(cmp.EXPORTS) and len(declared) == 17
-    declared_mpe = set(re.findall(r"\b(mpe_[a-z_]+)\s*\(", open(MPE_HEADER).read()))
-    assert declared_mpe == set(cmp.MPE_EXPORTS)
-    for name in declared | declared_mpe:
-        assert getattr(lib, name) is not None
+    from defuse_amd import mpe
+    assert abi.check_functions("defuse_cmp.h", cmp, r"cmp_[a-z_]+") == 17
+    assert cmp.MPE_EXPORTS is mpe.EXPORTS
+    assert abi.check_functions("defuse_mpe.h", mpe, r"mpe_[a-z_]+") == len(cmp.MPE_EXPORTS)
 
 
-def test_cmp_struct_layouts_match_header(cmp, tmp_path):
-    """sizeof and offsetof of every struct of the two headers, as a C compiler sees them, against the ctypes structs, and the
-    numpy dtypes against the ctypes structs."""
-    structs = dict(cmp.STRUCTS, **cmp.MPE_STRUCTS)
-    lines = []
-    for cname, st in structs.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "%s"\n#include "%s"\nint main(void) { %s return 0; }\n' % (HEADER, MPE_HEADER, " ".join(lines)))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-o", str(exe), str(src)])
-    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(got) == len(structs)
-    for line, (cname, st) in zip(got, structs.items()):
-        want = "%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_)
-        assert line == want
-    for cname, dt in cmp.DTYPES.items():
-        st = cmp.STRUCTS[cname]
-        assert dt.itemsize == ctypes.sizeof(st) and [dt.fields[f][1] for f, _ in st._fields_] == [getattr(st, f).offset for f, _ in st._fields_], cname
+def test_cmp_struct_layouts_match_header(cmp):
+    """sizeof and offsetof of every struct of the two headers, as a C++ and a C compiler see them, against the ctypes structs,
+    and the numpy dtypes against the ctypes structs."""
+    from defuse_amd import mpe
+    assert cmp.MPE_STRUCTS is mpe.STRUCTS and (cmp.MpeParams, cmp.MpeTiming) == tuple(mpe.STRUCTS.values())
+    abi.check("defuse_mpe.h", mpe, r"mpe_[a-z_]+")
+    abi.check("defuse_cmp.h", cmp, r"cmp_[a-z_]+", dtypes=[(cmp.STRUCTS[cname], dt) for cname, dt in cmp.DTYPES.items()])
     assert (ctypes.sizeof(cmp.Row), ctypes.sizeof(cmp.ProblemCounts), ctypes.sizeof(cmp.ProblemsDevice)) == (52, 32, 96)
 
 

@@ -17,6 +17,7 @@ import types
 import numpy as np
 import pytest
 
+from tests import abi
 from tests import config1_case as c1
 from tests import pipeline_case
 from tests.eval_case import generated_case
@@ -145,34 +146,20 @@ def _c_struct(name):
 def test_header_and_binding_agree(built):
     """eval_group and eval_timing: the binding's fields are the header's, in order, with its types, sizes and offsets; the
     library exports every function the header declares."""
-    from defuse_amd import dsa
     from defuse_amd import eval as ev
     ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-    size = {"int32_t": 4, "int64_t": 8, "float": 4, "double": 8}
-    for name, struct_, total in (("eval_group", ev.EvalGroup, 72), ("eval_timing", ev.EvalTiming, 56)):
-        fields = _c_struct(name)
-        assert [(n, ctype[t]) for n, t in fields] == list(struct_._fields_), name
-        off = 0
-        for n, t in fields:                                         # natural alignment, as the C compiler lays it out
-            off = (off + size[t] - 1) // size[t] * size[t]
-            assert getattr(struct_, n).offset == off, (name, n)
-            off += size[t]
-        assert ctypes.sizeof(struct_) == total == (off + 7) // 8 * 8
+    for name, struct_ in (("eval_group", ev.EvalGroup), ("eval_timing", ev.EvalTiming)):
+        assert [(n, ctype[t]) for n, t in _c_struct(name)] == list(struct_._fields_), name
+    sizes, n = abi.check("defuse_eval.h", ev, r"eval_\w+", constants={"EVAL_NO_SPLIT": ev.NO_SPLIT, "EVAL_HOST_STATS": ev.HOST_STATS},
+                         dtypes=[(ev.EvalGroup, ev.GROUP_DTYPE)])
+    assert sizes == [72, 56] and n == 6
     assert ev.GROUP_DTYPE.itemsize == 72
-    assert [(n, ev.GROUP_DTYPE.fields[n][1]) for n in ev.GROUP_DTYPE.names] == [(n, getattr(ev.EvalGroup, n).offset) for n, _ in ev.EvalGroup._fields_]
-    header = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = re.findall(r"\b(eval_\w+)\s*\(", header)
-    assert sorted(declared) == sorted(ev.EXPORTS) and len(declared) == 6
-    lib = dsa.load_library()
-    for fn in declared:
-        assert hasattr(lib, fn), fn
-    assert (ev.NO_SPLIT, ev.HOST_STATS) == tuple(int(re.search(r"#define %s\s+(\d+)" % m, header).group(1)) for m in ("EVAL_NO_SPLIT", "EVAL_HOST_STATS"))
 
 
 def test_argument_errors_without_a_device(built):
     from defuse_amd import dsa
     from defuse_amd import eval as ev
-    lib = ev._bind(dsa.load_library())
+    lib = ev.lib()
     h = ctypes.c_void_p()
     devices = [999] + ([0] if lib.dsa_device_count() == 0 else [])
     for d in devices:

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import cases
+from tests import abi, cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOKE = os.path.join(ROOT, "tests", "golden", "smoke")
@@ -85,11 +85,7 @@ def test_library_exports(built):
     import re
     from defuse_amd import dsa
     lib = ctypes.CDLL(dsa.LIB_PATH)
-    header = open(os.path.join(ROOT, "include", "defuse_dsa.h")).read()
-    declared = set(re.findall(r"\b(dsa_[a-z_]+)\s*\(", header))
-    assert declared == set(dsa.EXPORTS)
-    for name in declared:
-        assert getattr(lib, name) is not None
+    abi.check_functions("defuse_dsa.h", dsa, r"dsa_[a-z_]+")
     assert b"gfx950" in ctypes.cast(lib.dsa_version, ctypes.CFUNCTYPE(ctypes.c_char_p))()
     # and every function the other headers of include/ declare
     for h, prefix in (("defuse_sc.h", "sc"), ("defuse_mpe.h", "mpe"), ("defuse_la.h", "la"), ("defuse_hc.h", "hc"), ("defuse_cov.h", "cov"), ("defuse_cmp.h", "cmp")):
@@ -110,7 +106,11 @@ def test_no_cpu_fallback_without_gpu(built):
 
 
 def test_struct_layouts_match_header(built):
-    from defuse_amd import dsa
+    from defuse_amd import capi, dsa
+    codes = {"DSA_E_CAPACITY": capi.E_CAPACITY, "DSA_E_DEVICE": capi.E_DEVICE, "DSA_E_ARG": capi.E_ARG, "DSA_E_LIMIT": capi.E_LIMIT,
+             "DSA_E_BUSY": capi.E_BUSY, "DSA_PLAN_NO_REORDER": dsa.PLAN_NO_REORDER, "DSA_PLAN_NO_RANK": dsa.PLAN_NO_RANK,
+             "DSA_PLAN_NO_TIGHTEN": dsa.PLAN_NO_TIGHTEN, "DSA_PLAN_NO_LPT": dsa.PLAN_NO_LPT}
+    assert abi.check("defuse_dsa.h", dsa, r"dsa_[a-z_]+", constants=codes)[0] == [12, 56, 96]
     assert dsa.FUSION_DTYPE.itemsize == 20 and dsa.PAIR_DTYPE.itemsize == 20 and dsa.RECORD_DTYPE.itemsize == 40
     assert ctypes.sizeof(dsa.Timing) == 56 and ctypes.sizeof(dsa.Limits) == 12      # dsa_timing grew by plan_ms + pad_
     # dsa_kernel_counts: the binding's fields in the header's order, twelve 64-bit words

@@ -5,18 +5,17 @@ with the status rules of the header (no task, no split, the two DebugChecks) app
 chains the golden break and sequence files.  The averages are compared as bit patterns."""
 import ctypes
 import os
-import re
 import struct
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+from tests import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOKE = os.path.join(ROOT, "tests", "golden", "smoke")
 CONFIG1 = os.path.join(ROOT, "tests", "golden", "config1")
-HEADER = os.path.join(ROOT, "include", "defuse_pred.h")
 E_CAPACITY, E_DEVICE, E_ARG, E_LIMIT = -1, -2, -3, -4
 NO_SPLIT, HOST_STATS, NO_TASK, OUT_OF_WINDOW = 1, 2, 4, 8
 ODD_BYTES = b"ACGTNacgtn.\x00\xff*"
@@ -179,57 +178,20 @@ class Store:
 
 
 # ---------------------------------------------------------------------------------------------- without a GPU
-def test_pred_header_and_binding_agree(pred, tmp_path):
-    """sizeof and offsetof of every struct of the header, as a C++ compiler sees them, against the ctypes structs and the
-    numpy dtypes; the PRED_* values; every declared function bound and exported; the other headers' counts unchanged."""
-    lines = []
-    for cname, st in pred.STRUCTS.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    lines.append('printf("%d %d\\n", PRED_NO_TASK, PRED_OUT_OF_WINDOW);')
-    src = tmp_path / "layout.cpp"
-    src.write_text('#include <cstddef>\n#include <cstdio>\n#include "%s"\nint main() { %s }\n' % (HEADER, " ".join(lines)))
-    exe = tmp_path / "layout"
-    subprocess.check_call(["g++", "-std=c++17", "-o", str(exe), str(src)])
-    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(got) == len(pred.STRUCTS) + 1
-    for line, (cname, st) in zip(got, pred.STRUCTS.items()):
-        want = "%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_)
-        assert line == want
-    assert got[-1] == "%d %d" % (pred.NO_TASK, pred.OUT_OF_WINDOW) == "4 8"
-    for st, dt in ((pred.Task, pred.TASK_DTYPE), (pred.Result, pred.RESULT_DTYPE)):
-        assert ctypes.sizeof(st) == dt.itemsize == 56 and dt.itemsize % 8 == 0
-        assert [(f, getattr(st, f).offset) for f, _ in st._fields_] == [(f, dt.fields[f][1]) for f in dt.names]
+def test_pred_header_and_binding_agree(pred):
+    """sizeof and offsetof of every struct of the header, as g++ and gcc -std=c99 see them, against the ctypes structs and the
+    numpy dtypes; the PRED_* values; every declared function bound and exported."""
+    sizes, n = abi.check("defuse_pred.h", pred, r"pred_[a-z_]+", constants={"PRED_NO_TASK": pred.NO_TASK, "PRED_OUT_OF_WINDOW": pred.OUT_OF_WINDOW},
+                         dtypes=[(pred.Task, pred.TASK_DTYPE), (pred.Result, pred.RESULT_DTYPE)])
+    assert (pred.NO_TASK, pred.OUT_OF_WINDOW) == (4, 8)
+    assert sizes == [56, 56, 40, 40] and n == 10
+    assert pred.TASK_DTYPE.itemsize == pred.RESULT_DTYPE.itemsize == 56
     assert (ctypes.sizeof(pred.View), ctypes.sizeof(pred.PredTiming)) == (40, 40)
-    # the same C compiler's view, as plain C: the header is a C header
-    csrc = tmp_path / "plain.c"
-    csrc.write_text('#include "%s"\nint main(void) { return (int)sizeof(pred_task) - 56; }\n' % HEADER)
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "plain"), str(csrc)])
-    assert subprocess.run([str(tmp_path / "plain")]).returncode == 0
-
-    from defuse_amd import dsa
-    lib = ctypes.CDLL(dsa.LIB_PATH)
-    declared = set(re.findall(r"\b(pred_[a-z_]+)\s*\(", open(HEADER).read()))
-    assert declared == set(pred.EXPORTS) and len(declared) == 10
-    for name in declared:
-        assert getattr(lib, name) is not None
-    inc = os.path.join(ROOT, "include")
-    count = lambda h, pat: len(set(re.findall(pat, open(os.path.join(inc, h)).read())))
-    assert count("defuse_eval.h", r"\b(eval_\w+)\s*\(") == 6
-    assert count("defuse_bat.h", r"\b((?:bat|cand)_[a-z_]+)\s*\(") == 14
-    from defuse_amd import bat, cand
-    from defuse_amd import eval as ev
-    assert len(ev.EXPORTS) == 6 and len(bat.EXPORTS) == 14
-    assert count("defuse_cand.h", r"\b(cand_[a-z_]+)\s*\(") == len(cand.EXPORTS)
-    for h in ("defuse_eval.h", "defuse_bat.h", "defuse_cand.h"):
-        assert "pred_" not in open(os.path.join(inc, h)).read()
 
 
 def test_pred_argument_errors_need_no_device(pred):
     from defuse_amd import eval as ev
-    lib = pred._bind(pred.load_library())
+    lib = pred.lib()
     err = lambda: lib.pred_last_error().decode()
     h = ctypes.c_void_p()
     one = ctypes.c_void_p(1)           # stands for an object: the argument errors are found before any is looked at

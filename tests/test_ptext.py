@@ -6,18 +6,18 @@ applied around them by `host_texts` below; for the chains the golden files."""
 import ctypes
 import math
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
+
+from tests import abi
 
 from tests.test_pred import Store, make_task, random_case, rec, records_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOKE = os.path.join(ROOT, "tests", "golden", "smoke")
 CONFIG1 = os.path.join(ROOT, "tests", "golden", "config1")
-HEADER = os.path.join(ROOT, "include", "defuse_ptext.h")
 E_CAPACITY, E_DEVICE, E_ARG, E_LIMIT = -1, -2, -3, -4
 NO_SPLIT, HOST_STATS, NO_TASK, OUT_OF_WINDOW, HOST_SEQ = 1, 2, 4, 8, 16
 
@@ -122,56 +122,18 @@ def g_values(n_random):
 
 
 # ---------------------------------------------------------------------------------------------- without a GPU
-def test_ptext_header_and_binding_agree(ptext, tmp_path):
+def test_ptext_header_and_binding_agree(ptext):
     """sizeof and offsetof of every struct of the header, as g++ and gcc -std=c99 see them, against the ctypes structs and
-    the numpy dtypes; PTEXT_HOST_SEQ; every declared function bound and exported; the other headers' counts unchanged."""
-    lines = []
-    for cname, st in ptext.STRUCTS.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    lines.append('printf("%d\\n", PTEXT_HOST_SEQ);')
-    want = ["%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_) for cname, st in ptext.STRUCTS.items()]
-    want.append("%d" % ptext.HOST_SEQ)
-    body = '#include <stddef.h>\n#include <stdio.h>\n#include "%s"\nint main(void) { %s return 0; }\n' % (HEADER, " ".join(lines))
-    for name, cmd in (("layout.cpp", ["g++", "-std=c++17"]), ("layout.c", ["gcc", "-std=c99", "-Wall", "-Werror"])):
-        src = tmp_path / name
-        src.write_text(body)
-        exe = tmp_path / (name + ".exe")
-        subprocess.check_call(cmd + ["-o", str(exe), str(src)])
-        assert subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines() == want, name
+    the numpy dtypes; PTEXT_HOST_SEQ; every declared function bound and exported."""
+    sizes, n = abi.check("defuse_ptext.h", ptext, r"ptext_[a-z_]+", constants={"PTEXT_HOST_SEQ": ptext.HOST_SEQ},
+                         dtypes=[(ptext.End, ptext.END_DTYPE), (ptext.Line, ptext.LINE_DTYPE)])
     assert ptext.HOST_SEQ == 16 and ptext.HOST_SEQ & (NO_SPLIT | HOST_STATS | NO_TASK | OUT_OF_WINDOW) == 0
-    for st, dt in ((ptext.End, ptext.END_DTYPE), (ptext.Line, ptext.LINE_DTYPE)):
-        assert ctypes.sizeof(st) == dt.itemsize and dt.itemsize % 8 == 0
-        assert [(f, getattr(st, f).offset) for f, _ in st._fields_] == [(f, dt.fields[f][1]) for f in dt.names]
-    assert [ctypes.sizeof(s) for s in ptext.STRUCTS.values()] == [16, 40, 56, 48]
-
-    from defuse_amd import dsa
-    lib = ctypes.CDLL(dsa.LIB_PATH)
-    declared = set(re.findall(r"\b(ptext_[a-z_]+)\s*\(", open(HEADER).read()))
-    assert declared == set(ptext.EXPORTS) and len(declared) == 10
-    for name in declared:
-        assert getattr(lib, name) is not None
-    bound = ptext._bind(ptext.load_library())
-    for name in declared - {"ptext_last_error"}:
-        assert getattr(bound, name).argtypes is not None, name
-    inc = os.path.join(ROOT, "include")
-    count = lambda h, pat: len(set(re.findall(pat, open(os.path.join(inc, h)).read())))
-    assert count("defuse_pred.h", r"\b(pred_[a-z_]+)\s*\(") == 10
-    assert count("defuse_eval.h", r"\b(eval_\w+)\s*\(") == 6
-    assert count("defuse_bat.h", r"\b((?:bat|cand)_[a-z_]+)\s*\(") == 14
-    rec_text = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "defuse_rec.h")).read(), flags=re.S)          # (as tests/test_records.py counts them)
-    assert len(set(re.findall(r"\b(rec_[a-z_]+)\s*\(", rec_text))) == 14
-    from defuse_amd import cand
-    assert count("defuse_cand.h", r"\b(cand_[a-z_]+)\s*\(") == len(cand.EXPORTS)
-    for h in sorted(os.listdir(inc)):
-        if h != "defuse_ptext.h":
-            assert "ptext_" not in open(os.path.join(inc, h)).read().replace("ptext_shared", ""), h
+    assert ptext.END_DTYPE.itemsize % 8 == 0 and ptext.LINE_DTYPE.itemsize % 8 == 0
+    assert sizes == [16, 40, 56, 48] and n == 10
 
 
 def test_ptext_argument_errors_need_no_device(ptext):
-    lib = ptext._bind(ptext.load_library())
+    lib = ptext.lib()
     err = lambda: lib.ptext_last_error().decode()
     h = ctypes.c_void_p()
     one = ctypes.c_void_p(1)           # stands for an object: the argument errors are found before any is looked at

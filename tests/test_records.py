@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import abi
 from tests import rec_case as rc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,31 +25,20 @@ DSA_E_CAPACITY, DSA_E_DEVICE, DSA_E_ARG, DSA_E_LIMIT = -1, -2, -3, -4
 # ---------------------------------------------------------------------------------------------- CPU
 def test_header_and_binding_agree(built):
     """rec_timing: the binding's fields are the header's, in order, with its types and offsets; every prototype of the header
-    is in rec.EXPORTS and exported by the library."""
-    from defuse_amd import dsa, rec
-    text = open(HEADER).read()
-    body = re.search(r"typedef struct rec_timing \{(.*?)\} rec_timing;", text, re.S).group(1)
+    is in rec.EXPORTS, bound and exported by the library."""
+    from defuse_amd import rec
+    body = re.search(r"typedef struct rec_timing \{(.*?)\} rec_timing;", open(HEADER).read(), re.S).group(1)
     fields = [(n, t) for t, n in re.findall(r"(int32_t|int64_t|float|double)\s+(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))]
     ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-    size = {"int32_t": 4, "int64_t": 8, "float": 4, "double": 8}
     assert [(n, ctype[t]) for n, t in fields] == list(rec.RecTiming._fields_)
-    off = 0
-    for n, t in fields:                                             # natural alignment, as the C compiler lays it out
-        off = (off + size[t] - 1) // size[t] * size[t]
-        assert getattr(rec.RecTiming, n).offset == off, n
-        off += size[t]
-    assert ctypes.sizeof(rec.RecTiming) == 56 == (off + 7) // 8 * 8
-    declared = re.findall(r"\b(rec_[a-z_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-    assert sorted(declared) == sorted(rec.EXPORTS) and len(declared) == 14
-    lib = dsa.load_library()
-    for fn in declared:
-        assert hasattr(lib, fn), fn
+    sizes, n = abi.check("defuse_rec.h", rec, r"rec_[a-z_]+")
+    assert sizes == [56] and n == 14
     assert rec.FIELDS == rc.FIELDS and rec.MAX_LINE == 9 * 12 + 1
 
 
 def test_argument_errors_without_a_device(built):
     from defuse_amd import dsa, rec
-    lib = rec._bind(dsa.load_library())
+    lib = rec.lib()
     h = ctypes.c_void_p()
     for d in [999] + ([0] if lib.dsa_device_count() == 0 else []):
         assert lib.rec_create(d, ctypes.byref(h)) == DSA_E_DEVICE and not h.value

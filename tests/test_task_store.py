@@ -7,16 +7,16 @@ edges it is about."""
 import ctypes
 import os
 import random
-import re
 import subprocess
 from collections import OrderedDict
 
 import numpy as np
 import pytest
 
+from tests import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOKE = os.path.join(ROOT, "tests", "golden", "smoke")
-HEADER = os.path.join(ROOT, "include", "defuse_task.h")
 E_CAPACITY, E_DEVICE, E_ARG, E_LIMIT = -1, -2, -3, -4
 PLUS, MINUS = 0, 1
 ODD_BYTES = b"ACGTNacgtn.\x00\xff*"
@@ -388,55 +388,24 @@ def random_case(seed):
 
 
 # ---------------------------------------------------------------------------------------------- without a GPU
-def test_task_header_and_binding_agree(task, tmp_path):
+def test_task_header_and_binding_agree(task):
     """sizeof and offsetof of every struct of the header, as g++ and gcc -std=c99 see them, against the ctypes structs and
-    the numpy dtypes; the constants; every declared function bound and exported; the other chain headers' counts unchanged."""
-    lines = []
-    for cname, st in task.STRUCTS.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    lines.append('printf("%d %d %d %d %d %d %d %d %d\\n", TASK_NO_SEQUENCE_0, TASK_BAD_CHROMOSOME_0, TASK_NO_SEQUENCE_1, TASK_BAD_CHROMOSOME_1, '
-                 'TASK_MAX_COORD, TASK_MAX_REGION, TASK_MAX_PARAM, TASK_MAX_SEQ_LEN, TASK_EXON_BIN);')
-    body = '#include <stddef.h>\n#include <stdio.h>\n#include "%s"\nint main(void) { %s return 0; }\n' % (HEADER, " ".join(lines))
-    outs = []
-    for src, cmd in (("layout.cpp", ["g++", "-std=c++17"]), ("layout.c", ["gcc", "-std=c99", "-Wall", "-Werror"])):
-        (tmp_path / src).write_text(body)
-        exe = str(tmp_path / (src + ".exe"))
-        subprocess.check_call(cmd + ["-o", exe, str(tmp_path / src)])
-        outs.append(subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert outs[0] == outs[1] and len(outs[0]) == len(task.STRUCTS) + 1
-    for line, (cname, st) in zip(outs[0], task.STRUCTS.items()):
-        assert line == "%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_)
-    assert outs[0][-1] == "%d %d %d %d %d %d %d %d %d" % (task.NO_SEQUENCE_0, task.BAD_CHROMOSOME_0, task.NO_SEQUENCE_1, task.BAD_CHROMOSOME_1,
-                                                       task.MAX_COORD, task.MAX_REGION, task.MAX_PARAM, task.MAX_SEQ_LEN, task.EXON_BIN)
-    assert outs[0][-1].startswith("1 2 4 8 ")
-    for st, dt, size in ((task.Pair, task.PAIR_DTYPE, 52), (task.Record, task.RECORD_DTYPE, 80), (task.End, task.END_DTYPE, 24), (task.Seq, task.SEQ_DTYPE, 16),
-                         (task.Transcript, task.TRANSCRIPT_DTYPE, 20), (task.Exon, task.EXON_DTYPE, 8)):
+    the numpy dtypes; the constants; every declared function bound and exported."""
+    consts = {"TASK_NO_SEQUENCE_0": task.NO_SEQUENCE_0, "TASK_BAD_CHROMOSOME_0": task.BAD_CHROMOSOME_0, "TASK_NO_SEQUENCE_1": task.NO_SEQUENCE_1,
+              "TASK_BAD_CHROMOSOME_1": task.BAD_CHROMOSOME_1, "TASK_MAX_COORD": task.MAX_COORD, "TASK_MAX_REGION": task.MAX_REGION,
+              "TASK_MAX_PARAM": task.MAX_PARAM, "TASK_MAX_SEQ_LEN": task.MAX_SEQ_LEN, "TASK_EXON_BIN": task.EXON_BIN}
+    pairs = ((task.Pair, task.PAIR_DTYPE, 52), (task.Record, task.RECORD_DTYPE, 80), (task.End, task.END_DTYPE, 24), (task.Seq, task.SEQ_DTYPE, 16),
+             (task.Transcript, task.TRANSCRIPT_DTYPE, 20), (task.Exon, task.EXON_DTYPE, 8))
+    sizes, n = abi.check("defuse_task.h", task, r"task_[a-z_]+", constants=consts, dtypes=[(st, dt) for st, dt, _ in pairs])
+    assert "%d %d %d %d " % tuple(consts.values())[:4] == "1 2 4 8 "
+    for st, dt, size in pairs:
         assert ctypes.sizeof(st) == dt.itemsize == size
-        assert [(f, getattr(st, f).offset) for f, _ in st._fields_] == [(f, dt.fields[f][1]) for f in dt.names]
     assert (ctypes.sizeof(task.Params), ctypes.sizeof(task.Counts), ctypes.sizeof(task.TaskTiming)) == (16, 32, 64)
-
-    from defuse_amd import bat, cand, dsa, pred
-    from defuse_amd import eval as ev
-    lib = ctypes.CDLL(dsa.LIB_PATH)
-    declared = set(re.findall(r"\b(task_[a-z_]+)\s*\(", open(HEADER).read()))
-    assert declared == set(task.EXPORTS) and len(declared) == 12
-    for name in declared:
-        assert getattr(lib, name) is not None
-    inc = os.path.join(ROOT, "include")
-    count = lambda h, pat: len(set(re.findall(pat, open(os.path.join(inc, h)).read())))
-    assert count("defuse_eval.h", r"\b(eval_\w+)\s*\(") == 6 == len(ev.EXPORTS)
-    assert count("defuse_bat.h", r"\b((?:bat|cand)_[a-z_]+)\s*\(") == 14 == len(bat.EXPORTS)
-    assert count("defuse_pred.h", r"\b(pred_[a-z_]+)\s*\(") == 10 == len(pred.EXPORTS)
-    assert count("defuse_cand.h", r"\b(cand_[a-z_]+)\s*\(") == 8 == len(cand.EXPORTS)
-    for h in ("defuse_eval.h", "defuse_bat.h", "defuse_cand.h", "defuse_pred.h"):
-        assert "task_" not in open(os.path.join(inc, h)).read()
+    assert len(sizes) == 9 and n == 12
 
 
 def test_task_argument_errors_need_no_device(task):
-    lib = task._bind(task.load_library())
+    lib = task.lib()
     err = lambda: lib.task_last_error().decode()
     h = ctypes.c_void_p()
     one = ctypes.c_void_p(1)           # stands for an object: the argument errors are found before any is looked at

@@ -6,18 +6,17 @@ to ParseSamLine / FastqReader::next / field_int of tools_src/defuse_host.hpp; fo
 bat_reads_create on the oracle's arrays; for the chain the same chain fed from host-parsed arrays."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import abi
 from tests import pipeline_case
 from tests import text_oracle as ora
 from tests.test_batch_assembly import DeviceArray, assert_same_batch, from_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "defuse_text.h")
 E_CAPACITY, E_DEVICE, E_ARG, E_LIMIT = -1, -2, -3, -4
 NAMES = [b"chr1", b"chr10", b"chr1_x", b"chr2", b"ENSG01|ENST01"]
 SAM_FIELDS = ("consumed", "n_lines", "n_alignments", "stop_line", "n_bad_fragment", "stop_kind", "carry_out")
@@ -133,54 +132,23 @@ def check_fastq_files(ctx, text, files, max_read_len=None):
 
 
 # ---------------------------------------------------------------------------------------------- without a GPU
-def test_text_header_and_binding_agree(text, tmp_path):
+def test_text_header_and_binding_agree(text):
     """sizeof and offsetof of every struct of the header, as g++ and gcc -std=c99 see them, against the ctypes structs and
-    the numpy dtypes; every declared function bound and exported; nothing of it in the older headers."""
-    lines = []
-    for cname, st in text.STRUCTS.items():
-        lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))
-        for f, _ in st._fields_:
-            lines.append('printf(" %s:%%zu", offsetof(%s, %s));' % (f, cname, f))
-        lines.append('printf("\\n");')
-    lines.append('printf("%d %d %d %d %d\\n", TXT_MAX_READ_LEN, TXT_SAM_EMPTY_LINE, TXT_SAM_BAD_QNAME, TXT_FASTQ_BAD_NAME, TXT_FASTQ_LONG_READ);')
-    want = ["%s %d" % (cname, ctypes.sizeof(st)) + "".join(" %s:%d" % (f, getattr(st, f).offset) for f, _ in st._fields_) for cname, st in text.STRUCTS.items()]
-    want.append("%d %d %d %d %d" % (text.MAX_READ_LEN, text.SAM_EMPTY_LINE, text.SAM_BAD_QNAME, text.FASTQ_BAD_NAME, text.FASTQ_LONG_READ))
-    body = '#include <stddef.h>\n#include <stdio.h>\n#include "%s"\nint main(void) { %s return 0; }\n' % (HEADER, " ".join(lines))
-    for name, cmd in (("layout.cpp", ["g++", "-std=c++17"]), ("layout.c", ["gcc", "-std=c99", "-Wall", "-Werror"])):
-        src = tmp_path / name
-        src.write_text(body)
-        exe = tmp_path / (name + ".exe")
-        subprocess.check_call(cmd + ["-o", str(exe), str(src)])
-        assert subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines() == want, name
-    for st, dt in ((text.SamResult, text.SAM_RESULT_DTYPE), (text.FastqResult, text.FASTQ_RESULT_DTYPE)):
-        assert ctypes.sizeof(st) == dt.itemsize and dt.itemsize % 8 == 0
-        assert [(f, getattr(st, f).offset) for f, _ in st._fields_] == [(f, dt.fields[f][1]) for f in dt.names]
-    assert [ctypes.sizeof(s) for s in text.STRUCTS.values()] == [48, 32, 40, 40, 48]
+    the numpy dtypes; every declared function bound and exported."""
+    consts = {"TXT_MAX_READ_LEN": text.MAX_READ_LEN, "TXT_SAM_EMPTY_LINE": text.SAM_EMPTY_LINE, "TXT_SAM_BAD_QNAME": text.SAM_BAD_QNAME,
+              "TXT_FASTQ_BAD_NAME": text.FASTQ_BAD_NAME, "TXT_FASTQ_LONG_READ": text.FASTQ_LONG_READ}
+    sizes, n = abi.check("defuse_text.h", text, r"(?:txt|cand|bat)_[a-z_]+", constants=consts,
+                         dtypes=[(text.SamResult, text.SAM_RESULT_DTYPE), (text.FastqResult, text.FASTQ_RESULT_DTYPE)])
+    assert text.SAM_RESULT_DTYPE.itemsize % 8 == 0 and text.FASTQ_RESULT_DTYPE.itemsize % 8 == 0
+    assert sizes == [48, 32, 40, 40, 48] and n == 17
     assert (text.ALIGNMENT_DTYPE.itemsize, text.READ_DTYPE.itemsize) == (24, 24)
-
-    from defuse_amd import bat, cand, dsa
-    lib = ctypes.CDLL(dsa.LIB_PATH)
-    header = open(HEADER).read()
-    declared = set(re.findall(r"\b((?:txt|cand|bat)_[a-z_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
-    assert declared == set(text.EXPORTS) and len(declared) == 17
-    for name in declared:
-        assert getattr(lib, name) is not None
-    bound = text._bind(text.load_library())
-    for name in declared - {"txt_last_error"}:
-        assert getattr(bound, name).argtypes is not None, name
-    assert "ptext_" not in header
-    assert not set(text.EXPORTS) & (set(bat.EXPORTS) | set(cand.EXPORTS))
-    inc = os.path.join(ROOT, "include")
-    for h in sorted(os.listdir(inc)):
-        if h != "defuse_text.h":
-            assert not re.search(r"\btxt_|cand_enumerate_resident|bat_reads_create_device", open(os.path.join(inc, h)).read()), h
     for method in ("parse_sam", "sam_alignments", "fastq_begin", "fastq_add", "fastq_fetch", "reads_store"):
         assert hasattr(text.Context, method)
     assert callable(text.enumerate_resident) and hasattr(text, "Names")
 
 
 def test_text_argument_errors_need_no_device(text, cand, bat):
-    lib = bat._bind(cand._bind(text._bind(text.load_library())))
+    lib = text.lib()
     err = lambda: lib.txt_last_error().decode()
     h = ctypes.c_void_p()
     one = ctypes.c_void_p(1)           # stands for an object or a buffer: the argument errors are found before any is looked at
