@@ -1,13 +1,14 @@
 // sc_api.hip — greedy set cover on gfx950 (include/defuse_sc.h), replacing SetCover() of
 // tools/setcover.cpp:30-110.  Integer/byte work: radix sort + component labelling are HBM-bound, the
-// per-component greedy is latency-bound; nothing here is shaped into a GEMM.
+// per-component greedy is latency-bound; nothing here is shaped into a GEMM.  The kernels and the run over
+// clusters in device memory are sc_shared.hpp's (sct_api.hip builds its clusters there); this file is the
+// host-pointer entry around them.
 #include <hip/hip_runtime.h>
 
 #include "hip_host.hpp"
-#include <hipcub/hipcub.hpp>
+#include "sc_shared.hpp"
 
 #include <string>
-#include <vector>
 
 #include "../../include/defuse_dsa.h"
 #include "../../include/defuse_sc.h"
@@ -17,193 +18,8 @@ namespace {
 using hiphost::DeviceBuffer;
 
 thread_local std::string g_err;    // sc_prepare runs on a helper thread beside the caller's sc_cover (tools_src/setcover.cpp)
-constexpr int SMALL_MAX = 32;   // components with more clusters than this get a whole wave
 
 #define SC_HIP(call) HIPHOST_TRY(g_err, call)
-
-// occurrence k of the input -> (element key, owning cluster)
-__global__ void k_occurrences(const int64_t* __restrict__ cluster_off, int32_t n_clusters, int32_t* __restrict__ occ_cluster)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n_clusters) return;
-    for (int64_t k = cluster_off[c]; k < cluster_off[c + 1]; ++k) occ_cluster[k] = c;
-}
-
-// e2c_off[e] = first position of key e in the sorted keys (lower bound); e2c_off[max_element+1] = n
-__global__ void k_lower_bounds(const int32_t* __restrict__ keys, int64_t n, int32_t max_element, int64_t* __restrict__ off)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e > (int64_t)max_element + 1) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)keys[mid] < e) lo = mid + 1; else hi = mid;
-    }
-    off[e] = lo;
-}
-
-__global__ void k_iota(int32_t* __restrict__ a, int32_t n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = i;
-}
-
-// root of c's tree.  label[x] <= x always (a hook only ever lowers a label), so the walk ends
-__device__ __forceinline__ int root_of(const int32_t* label, int c)
-{
-    int r = c, p;
-    while ((p = label[r]) != r) r = p;
-    return r;
-}
-
-// hook: every fragment hangs the ROOTS of its clusters' trees under the smallest of them.  Lowering the label of the cluster
-// itself would let a label advance one cluster per round along a chain of clusters; a root moves its whole tree.  In two
-// rounds a tree either hangs under another or has taken in every tree it touched, so the trees of a component halve every
-// two rounds and the number of rounds is logarithmic in the clusters, whatever the shape of the component.
-__global__ void k_hook(const int64_t* __restrict__ e2c_off, const int32_t* __restrict__ e2c, int32_t max_element,
-                       int32_t* label, int* __restrict__ changed)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e > max_element) return;
-    const int64_t b = e2c_off[e], en = e2c_off[e + 1];
-    if (en - b < 2) return;
-    int m = 0x7FFFFFFF;
-    for (int64_t k = b; k < en; ++k) m = min(m, root_of(label, e2c[k]));
-    for (int64_t k = b; k < en; ++k) {
-        const int r = root_of(label, e2c[k]);
-        if (r > m) {                            // m < r and in r's component: the forest stays a forest
-            atomicMin(&label[r], m);
-            *changed = 1;
-        }
-    }
-}
-
-// compress: every cluster jumps to its grandparent until its parent is a root.  No hook runs beside this kernel, so the
-// roots stand still and a lane writes its own label only; the jumps of the others shorten its way.
-__global__ void k_compress(int32_t* label, int32_t n)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    int p = label[c];
-    for (;;) {
-        const int g = label[p];
-        if (g == p) break;
-        label[c] = g;
-        p = g;
-    }
-}
-
-// segment heads of the (label-sorted) cluster list -> component table
-__global__ void k_mark_heads(const int32_t* __restrict__ sorted_label, int32_t n, int32_t* __restrict__ head_flag)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) head_flag[i] = (i == 0 || sorted_label[i] != sorted_label[i - 1]) ? 1 : 0;
-}
-__global__ void k_scatter_heads(const int32_t* __restrict__ head_flag, const int32_t* __restrict__ head_rank, int32_t n,
-                                int32_t* __restrict__ comp_begin)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && head_flag[i]) comp_begin[head_rank[i]] = i;
-    if (i == n - 1) comp_begin[head_rank[i] + head_flag[i]] = n;   // end sentinel
-}
-
-struct Greedy {
-    const int64_t* cluster_off;
-    const int32_t* elements;
-    const int64_t* e2c_off;
-    const int32_t* e2c;
-    const int32_t* comp_clusters;   // clusters sorted by (component, index)
-    const int32_t* comp_begin;
-    int32_t n_components;
-    int32_t* size;
-    int32_t* seq;
-    int32_t* owner;
-};
-
-// assignment step of tools/setcover.cpp:76-106 for the chosen cluster
-__device__ __forceinline__ void take_cluster(const Greedy& g, int best, int& counter)
-{
-    for (int64_t k = g.cluster_off[best]; k < g.cluster_off[best + 1]; ++k) {
-        const int e = g.elements[k];
-        if (g.owner[e] >= 0) continue;
-        g.owner[e] = best;
-        for (int64_t q = g.e2c_off[e]; q < g.e2c_off[e + 1]; ++q) {     // ascending cluster index, duplicates included
-            const int c2 = g.e2c[q];
-            g.size[c2] -= 1;
-            g.seq[c2] = ++counter;
-        }
-    }
-}
-
-// one lane per small component
-__global__ void k_greedy_small(Greedy g)
-{
-    const int comp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (comp >= g.n_components) return;
-    const int b = g.comp_begin[comp], e = g.comp_begin[comp + 1];
-    if (e - b > SMALL_MAX) return;
-    int counter = 0;
-    for (int i = b; i < e; ++i) {
-        const int c = g.comp_clusters[i];
-        g.size[c] = (int)(g.cluster_off[c + 1] - g.cluster_off[c]);
-        g.seq[c] = ++counter;                        // initial arrival order: ascending cluster index
-    }
-    for (;;) {
-        int best = -1, bs = -1, bq = -1;
-        for (int i = b; i < e; ++i) {
-            const int c = g.comp_clusters[i];
-            const int s = g.size[c], q = g.seq[c];
-            if (s > bs || (s == bs && q > bq)) { best = c; bs = s; bq = q; }
-        }
-        if (bs <= 0) break;
-        take_cluster(g, best, counter);
-    }
-}
-
-// one wave per large component: the arg-max over (size, arrival) is a wave reduction, the assignment
-// step stays sequential (its order defines the arrival stamps)
-__global__ void k_greedy_large(Greedy g, const int32_t* __restrict__ large_list, int32_t n_large)
-{
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    if (wave >= n_large) return;
-    const int comp = large_list[wave];
-    const int b = g.comp_begin[comp], e = g.comp_begin[comp + 1];
-    for (int i = b + lane; i < e; i += 64) {
-        const int c = g.comp_clusters[i];
-        g.size[c] = (int)(g.cluster_off[c + 1] - g.cluster_off[c]);
-        g.seq[c] = i - b + 1;
-    }
-    int counter = e - b;
-    __threadfence_block();
-    for (;;) {
-        long long key = -1;                           // (size << 32 | seq), cluster carried alongside
-        int best = -1;
-        for (int i = b + lane; i < e; i += 64) {
-            const int c = g.comp_clusters[i];
-            const long long k = ((long long)g.size[c] << 32) | (unsigned)g.seq[c];
-            if (k > key) { key = k; best = c; }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const long long ok = __shfl_xor(key, d, 64);
-            const int ob = __shfl_xor(best, d, 64);
-            if (ok > key) { key = ok; best = ob; }
-        }
-        if ((key >> 32) <= 0) break;                  // wave-uniform after the butterfly
-        if (lane == 0) take_cluster(g, best, counter);
-        __threadfence_block();
-        counter = __shfl(counter, 0, 64);
-    }
-}
-
-__global__ void k_collect_large(const int32_t* __restrict__ comp_begin, int32_t n_components, int32_t* __restrict__ list,
-                                int32_t* __restrict__ n_large)
-{
-    const int comp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (comp >= n_components) return;
-    if (comp_begin[comp + 1] - comp_begin[comp] > SMALL_MAX) list[atomicAdd(n_large, 1)] = comp;
-}
 
 }  // namespace
 
@@ -229,94 +45,14 @@ extern "C" int sc_cover(int device, const int64_t* cluster_off, const int32_t* e
     for (int64_t e = 0; e <= max_element; ++e) owner[e] = -1;
     if (n_clusters == 0 || n_occ == 0) { if (timing) *timing = t; return DSA_OK; }
 
-    hiphost::Event ev[4];                 // destroyed on every return
-    for (auto& e : ev) SC_HIP(e.create());
-    DeviceBuffer<int64_t> d_coff, d_e2c_off;
-    DeviceBuffer<int32_t> d_el, d_occ_cluster, d_keys_sorted, d_e2c, d_label, d_label_sorted, d_idx, d_comp_clusters, d_flag, d_rank,
-        d_comp_begin, d_size, d_seq, d_owner, d_large, d_nlarge;
-    DeviceBuffer<int> d_changed;
-    DeviceBuffer<uint8_t> d_tmp;
+    DeviceBuffer<int64_t> d_coff;
+    DeviceBuffer<int32_t> d_el, d_owner;
     const int nel = max_element + 1;
-    SC_HIP(d_coff.reserve(n_clusters + 1)); SC_HIP(d_el.reserve(n_occ)); SC_HIP(d_occ_cluster.reserve(n_occ));
-    SC_HIP(d_keys_sorted.reserve(n_occ)); SC_HIP(d_e2c.reserve(n_occ)); SC_HIP(d_e2c_off.reserve(nel + 2));
-    SC_HIP(d_label.reserve(n_clusters)); SC_HIP(d_label_sorted.reserve(n_clusters)); SC_HIP(d_idx.reserve(n_clusters));
-    SC_HIP(d_comp_clusters.reserve(n_clusters)); SC_HIP(d_flag.reserve(n_clusters)); SC_HIP(d_rank.reserve(n_clusters));
-    SC_HIP(d_comp_begin.reserve(n_clusters + 2)); SC_HIP(d_size.reserve(n_clusters)); SC_HIP(d_seq.reserve(n_clusters));
-    SC_HIP(d_owner.reserve(nel)); SC_HIP(d_large.reserve(n_clusters)); SC_HIP(d_nlarge.reserve(1)); SC_HIP(d_changed.reserve(1));
+    SC_HIP(d_coff.reserve(n_clusters + 1)); SC_HIP(d_el.reserve(n_occ)); SC_HIP(d_owner.reserve(nel));
     SC_HIP(hipMemcpy(d_coff.p, cluster_off, (n_clusters + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     SC_HIP(hipMemcpy(d_el.p, elements, n_occ * sizeof(int32_t), hipMemcpyHostToDevice));
-    SC_HIP(hipMemset(d_owner.p, 0xFF, nel * sizeof(int32_t)));
-    const int B = 256;
-    auto grid = [&](int64_t n) { return dim3(hiphost::grid_of(n, B)); };
-
-    // 1. fragment -> clusters index: stable radix sort of the occurrences by fragment keeps each list in
-    //    ascending cluster order (the order tools/setcover.cpp:47-60 builds it in)
-    SC_HIP(hipEventRecord(ev[0]));
-    hipLaunchKernelGGL(k_occurrences, grid(n_clusters), dim3(B), 0, 0, d_coff.p, n_clusters, d_occ_cluster.p);
-    size_t tmp_bytes = 0, need = 0;
-    int bits = 1;
-    while ((1ll << bits) <= max_element) ++bits;
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_el.p, d_keys_sorted.p, d_occ_cluster.p, d_e2c.p, (int)n_occ, 0, bits));
-    tmp_bytes = need;
-    int cbits = 1;
-    while ((1ll << cbits) < n_clusters) ++cbits;
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_label.p, d_label_sorted.p, d_idx.p, d_comp_clusters.p, n_clusters, 0, cbits));
-    tmp_bytes = std::max(tmp_bytes, need);
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_flag.p, d_rank.p, n_clusters));
-    tmp_bytes = std::max(tmp_bytes, need);
-    SC_HIP(d_tmp.reserve(tmp_bytes));
-    need = tmp_bytes;
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_el.p, d_keys_sorted.p, d_occ_cluster.p, d_e2c.p, (int)n_occ, 0, bits));
-    hipLaunchKernelGGL(k_lower_bounds, grid(nel + 1), dim3(B), 0, 0, d_keys_sorted.p, n_occ, max_element, d_e2c_off.p);
-    SC_HIP(hipEventRecord(ev[1]));
-
-    // 2. connected components of the cluster/fragment graph: root hooking + full compression until a round hooks nothing
-    hipLaunchKernelGGL(k_iota, grid(n_clusters), dim3(B), 0, 0, d_label.p, n_clusters);
-    int iterations = 0;
-    for (;;) {
-        int changed = 0;
-        SC_HIP(hipMemset(d_changed.p, 0, sizeof(int)));
-        hipLaunchKernelGGL(k_hook, grid(nel), dim3(B), 0, 0, d_e2c_off.p, d_e2c.p, max_element, d_label.p, d_changed.p);
-        hipLaunchKernelGGL(k_compress, grid(n_clusters), dim3(B), 0, 0, d_label.p, n_clusters);
-        SC_HIP(hipMemcpy(&changed, d_changed.p, sizeof(int), hipMemcpyDeviceToHost));
-        ++iterations;
-        if (!changed) break;
-        if (iterations > 10000) { g_err = "connected components did not converge"; return DSA_E_DEVICE; }
-    }
-    // clusters grouped by component, ascending index inside a component (stable sort by label)
-    hipLaunchKernelGGL(k_iota, grid(n_clusters), dim3(B), 0, 0, d_idx.p, n_clusters);
-    need = tmp_bytes;
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, d_label.p, d_label_sorted.p, d_idx.p, d_comp_clusters.p, n_clusters, 0, cbits));
-    hipLaunchKernelGGL(k_mark_heads, grid(n_clusters), dim3(B), 0, 0, d_label_sorted.p, n_clusters, d_flag.p);
-    need = tmp_bytes;
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, need, d_flag.p, d_rank.p, n_clusters));
-    hipLaunchKernelGGL(k_scatter_heads, grid(n_clusters), dim3(B), 0, 0, d_flag.p, d_rank.p, n_clusters, d_comp_begin.p);
-    int last_rank = 0, last_flag = 0;
-    SC_HIP(hipMemcpy(&last_rank, d_rank.p + (n_clusters - 1), sizeof(int), hipMemcpyDeviceToHost));
-    SC_HIP(hipMemcpy(&last_flag, d_flag.p + (n_clusters - 1), sizeof(int), hipMemcpyDeviceToHost));
-    const int n_components = last_rank + last_flag;
-    SC_HIP(hipEventRecord(ev[2]));
-
-    // 3. greedy, independently per component
-    Greedy g{d_coff.p, d_el.p, d_e2c_off.p, d_e2c.p, d_comp_clusters.p, d_comp_begin.p, n_components, d_size.p, d_seq.p, d_owner.p};
-    SC_HIP(hipMemset(d_nlarge.p, 0, sizeof(int)));
-    hipLaunchKernelGGL(k_collect_large, grid(n_components), dim3(B), 0, 0, d_comp_begin.p, n_components, d_large.p, d_nlarge.p);
-    hipLaunchKernelGGL(k_greedy_small, grid(n_components), dim3(B), 0, 0, g);
-    int n_large = 0;
-    SC_HIP(hipMemcpy(&n_large, d_nlarge.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (n_large > 0)
-        hipLaunchKernelGGL(k_greedy_large, grid((int64_t)n_large * 64), dim3(B), 0, 0, g, d_large.p, n_large);
-    SC_HIP(hipEventRecord(ev[3]));
-    SC_HIP(hipDeviceSynchronize());
-    SC_HIP(hipGetLastError());
+    if (const int rc = sc_cover_device(g_err, nullptr, d_coff.p, d_el.p, n_clusters, n_occ, max_element, d_owner.p, t)) return rc;
     SC_HIP(hipMemcpy(owner, d_owner.p, nel * sizeof(int32_t), hipMemcpyDeviceToHost));
-    t.build_ms = hiphost::elapsed(ev[0], ev[1]);
-    t.components_ms = hiphost::elapsed(ev[1], ev[2]);
-    t.greedy_ms = hiphost::elapsed(ev[2], ev[3]);
-    t.total_ms = hiphost::elapsed(ev[0], ev[3]);
-    t.n_components = n_components;
-    t.n_large = n_large;
-    t.cc_iterations = iterations;
     if (timing) *timing = t;
     return DSA_OK;
 }

@@ -1,7 +1,8 @@
 // setcover — drop-in replacement of the reference tool (tools/setcover.cpp:112-147): same command
 // line, same cluster file format in and out, same progress lines on stdout.  ReadClusters /
 // WriteClusters follow tools/Parsers.cpp:23-170; SetCover itself runs on the GPU through
-// include/defuse_sc.h (no CPU fallback: without a HIP device the tool exits 1).
+// include/defuse_sc.h (no CPU fallback: without a HIP device the tool exits 1).  With DEFUSE_SC_DEVICE_TEXT=1 in
+// the environment the reading and writing run there too (the header's "cluster text" section).
 #include "../include/defuse_dsa.h"
 #include "../include/defuse_sc.h"
 #include "defuse_host.hpp"
@@ -126,6 +127,67 @@ int main(int argc, char* argv[])
         }
         die("Error: Invalid cluster ID for line " + std::to_string(lineNumber) + " of " + filename);
     };
+    // DEFUSE_SC_DEVICE_TEXT=1: the whole of the above and below on the device (include/defuse_sc.h, "cluster text").  The
+    // mapped file goes up in pieces of at most 1 GiB cut at line ends, the filtered file comes down in rounds; what the
+    // device reports becomes the progress lines, messages and exit codes of the host path.
+    if (const char* dt = std::getenv("DEFUSE_SC_DEVICE_TEXT"); dt && std::string(dt) == "1") {
+        auto fail = [&](const char* what) { die(std::string("Error: set cover on the GPU failed: ") + what + ": " + sct_last_error()); };
+        sct_ctx* ctx = nullptr;
+        if (sct_create(dsa_pick_device(), &ctx) != 0) fail("sct_create");
+        if (sct_begin(ctx) != 0) fail("sct_begin");
+        const size_t pieceBytes = (size_t)1 << 30;
+        for (size_t lo = 0; lo < text.size();) {
+            size_t hi = std::min(text.size(), lo + pieceBytes);
+            if (hi < text.size()) {
+                const void* nl = memrchr(text.data() + lo, '\n', hi - lo);
+                hi = nl ? (size_t)((const char*)nl - text.data()) + 1 : text.line_end(hi);      // (a line longer than a piece goes up whole)
+            }
+            int64_t consumed = 0;
+            if (sct_add(ctx, (const uint8_t*)text.data() + lo, (int64_t)(hi - lo), hi == text.size() ? 1 : 0, &consumed) != 0) fail("sct_add");
+            if ((size_t)consumed != hi - lo) die("Error: set cover on the GPU failed: a piece of the clusters file was not consumed whole");
+            lo = hi;
+        }
+        part("pieces on the device");
+        sct_result res;
+        if (sct_cover(ctx, (int64_t)minClusterSize, &res) != 0) fail("sct_cover");
+        if (timing) {
+            sct_timing t;
+            if (sct_get_timing(ctx, &t) == 0)
+                std::cerr << "[setcover] pieces " << t.n_pieces << ", upload " << t.upload_ms << " ms, tables " << t.tables_ms << " ms, parse " << t.parse_ms
+                          << " ms, layout " << t.layout_ms << " ms, cover " << t.cover_ms << " ms, select " << t.select_ms << " ms, gather " << t.gather_ms
+                          << " ms (" << t.gather_bytes << " bytes in " << t.n_runs << " runs), components " << t.n_components << " (large " << t.n_large
+                          << ")" << std::endl;
+        }
+        if (res.status == SCT_READ_STOP)
+            report(res.stop_kind, (size_t)res.stop_line, std::string(text.data() + res.stop_offset, (size_t)res.stop_len), inName);
+        stage("read");
+        std::cout << "Calculating set cover solution" << std::endl;
+        if (res.status == SCT_NEGATIVE_ELEMENT) die("Error: negative elements not permitted");
+        stage("set cover");
+        std::cout << "Writing out clusters" << std::endl;
+        OrderedFileWriter out;
+        if (!out.open_file(outName)) die("Error: unable to write to clusters file " + outName);
+        const int64_t roundBytes = (int64_t)1 << 28;
+        for (int64_t lo = 0; lo < res.out_bytes;) {
+            const int64_t hi = std::min(res.out_bytes, lo + roundBytes);
+            std::vector<std::string> texts(1);
+            texts[0].resize((size_t)(hi - lo));
+            if (sct_fetch(ctx, lo, (uint8_t*)&texts[0][0], hi - lo) != 0) fail("sct_fetch");
+            out.write_round_async(std::move(texts), 1);                 // copied into the file while the next round comes down
+            lo = hi;
+        }
+        out.wait_async();
+        if (res.status == SCT_WRITE_STOP)
+            report(res.stop_kind, (size_t)res.stop_line, std::string(text.data() + res.stop_offset, (size_t)res.stop_len), outName);
+        stage("write");
+        warm.join();
+        const int rc = out.close_file() ? 0 : 1;
+        std::cout.flush();
+        std::cerr.flush();
+        fflush(nullptr);
+        if (std::getenv("DEFUSE_FULL_EXIT")) exit(rc);
+        _exit(rc);
+    }
     run_threads(nThreads, [&](unsigned t) {
         Piece& pc = pieces[t];
         pc.members.reserve((cut[t + 1] - cut[t]) / 60 + 16);
