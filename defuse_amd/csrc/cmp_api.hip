@@ -282,6 +282,30 @@ int cmp_bin_upload_fragments(cmp_binner* b, const uint32_t* frag_start, int64_t 
     return DSA_OK;
 }
 
+// The device-pointer twins of the two uploads (the "cmpt" section of the header): device-to-device copies on the binner's
+// stream, complete on return, so that cmp_bin_run may follow from any thread.
+int cmpt_bin_upload_records_device(cmp_binner* b, const cmp_record* recs, int64_t n, int64_t at)
+{
+    if (!b || n < 0 || at < 0 || at + n > b->n_records || (n && !recs)) return DSA_E_ARG;
+    CMP_HIP(hipSetDevice(b->device));
+    if (n) {
+        CMP_HIP(hipMemcpyAsync(b->recs.p + at, recs, (size_t)n * sizeof(cmp_record), hipMemcpyDeviceToDevice, b->st));
+        CMP_HIP(hipStreamSynchronize(b->st));
+    }
+    return DSA_OK;
+}
+
+int cmpt_bin_upload_fragments_device(cmp_binner* b, const uint32_t* frag_start, int64_t n, int64_t at)
+{
+    if (!b || n < 0 || at < 0 || at + n > b->n_fragments + 1 || (n && !frag_start)) return DSA_E_ARG;
+    CMP_HIP(hipSetDevice(b->device));
+    if (n) {
+        CMP_HIP(hipMemcpyAsync(b->frag_start.p + at, frag_start, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, b->st));
+        CMP_HIP(hipStreamSynchronize(b->st));
+    }
+    return DSA_OK;
+}
+
 int cmp_bin_run(cmp_binner* b, int32_t mfr, cmp_stats* stats)
 {
     if (!b || !stats || mfr <= 0) return DSA_E_ARG;

@@ -758,4 +758,16 @@ int cmp_problems_rows(cmp_problems* p, cmp_row* rows, int64_t cap, int64_t* n_ro
     return DSA_OK;
 }
 
+// (the "cmpt" section of the header; cmp_problems_select has waited for the rows, so any stream may read them)
+int cmpt_problems_rows_view(cmp_problems* p, const cmp_row** rows_device, int64_t* n_rows)
+{
+    if (!p || !rows_device || !n_rows) return hiphost::fail(cmp_err(), DSA_E_ARG, "cmpt_problems_rows_view: null pointer");
+    *rows_device = nullptr;
+    *n_rows = 0;
+    if (p->n_rows < 0) return hiphost::fail(cmp_err(), DSA_E_ARG, "cmpt_problems_rows_view before a successful cmp_problems_select");
+    *rows_device = p->n_rows ? p->rows.p : nullptr;
+    *n_rows = p->n_rows;
+    return DSA_OK;
+}
+
 }  // extern "C"

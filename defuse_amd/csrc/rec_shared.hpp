@@ -63,9 +63,10 @@ REC_HD uint64_t rec_field_key(int32_t v)
 
 REC_HD int rec_field_length(int32_t v) { return rec_digits(rec_magnitude(v)) + (v < 0 ? 1 : 0) + 1; }
 
-// "%d\t" at out; returns the bytes written.  Division by the constant 10 only (a multiplication in the ISA).
+// "%d\t" at out (or "%d" and another closing byte: the last field of a line); returns the bytes written.  Division by the
+// constant 10 only (a multiplication in the ISA).
 template <typename Char>
-REC_HD int rec_write_field(int32_t v, Char* out)
+REC_HD int rec_write_field(int32_t v, Char* out, char close = '\t')
 {
     uint32_t m = rec_magnitude(v);
     int p = 0;
@@ -76,7 +77,7 @@ REC_HD int rec_write_field(int32_t v, Char* out)
         out[p + k] = (Char)('0' + (m - q * 10u));
         m = q;
     }
-    out[p + d] = '\t';
+    out[p + d] = (Char)close;
     return p + d + 1;
 }
 

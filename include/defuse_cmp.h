@@ -147,6 +147,99 @@ int  cmp_problems_select(cmp_problems* p, int64_t p0, int64_t p1, const int32_t*
  * rows may then be NULL). */
 int  cmp_problems_rows(cmp_problems* p, cmp_row* rows, int64_t cap, int64_t* n_rows);
 
+/* ---- Alignment and cluster text ("cmpt") ------------------------------------------------------------------------------
+ *
+ * The text on both sides of the objects above, on the device: the compact alignment file goes up as text and becomes the
+ * records, fragment starts and reference names the binner takes (CompactAlignmentStream and FragmentAlignmentStream,
+ * tools/AlignmentStream.cpp:156-221, with the name numbering of tools/clustermatepairs.cpp:430-446), and the rows of
+ * cmp_problems_select become the lines of the cluster file (OutputClusterMember, tools/clustermatepairs.cpp:376-387).
+ *
+ * Parse.  The text comes in pieces of at most 2^31 - 1 bytes.  Lines end at '\n' ('\r' belongs to its field).  With
+ * final = 0 an open last line is not consumed and `consumed` says where the next piece starts; with final = 1 it is a
+ * line.  Per line, in this order: length 0 stops with CMPT_EMPTY_LINE; fewer than six tab-separated fields with
+ * CMPT_FORMAT; a field 0 that is no integer (optional sign, digits only, int range) with CMPT_BAD_FRAGMENT; such a field
+ * 4 or 5 with CMPT_BAD_POSITION.  Fields behind the sixth are ignored.  The record is {fragment, start, end,
+ * CMP_META(ref, strand, read_end)} with read_end = (field 1 is "1") ? 0 : 1, strand = (field 3 is "-") ? 1 : 0 and ref the
+ * index of field 2 among the distinct names of the stream in order of first appearance, compared as exact bytes (an empty
+ * name is a name).  A line starts a fragment when the BYTES of its field 0 differ from those of the line before it ("7",
+ * "07" and "+7" are three fragments); the last line's field 0 is carried from piece to piece.  A stop ends the stream:
+ * records, fragments and names are those of the lines before it, and later pieces are passed over (consumed whole).
+ *
+ * Limits (DSA_E_LIMIT): a piece of more than 2^31 - 1 bytes, more than 2^32 - 1 records, more than max_names distinct
+ * names.  After a failed cmpt_add the stream is over: cmpt_begin starts the next one on the same context.
+ *
+ * Print.  Two lines per cmp_row, end 0 and then end 1:
+ *     cluster_id \t end \t fragment \t read_end \t name \t +|- \t start \t end \n
+ * integers as operator<<(int) prints them, names from the context's dictionary, strand 0 as '+' and any other as '-'.
+ * A ref outside the dictionary is DSA_E_ARG, and bad_row names the lowest such row.
+ *
+ * cmpt_last_error() has the text of a failed cmpt_ call on a context; the three entries that take a cmp_binner or a
+ * cmp_problems report through cmp_last_error(). */
+#define CMPT_EMPTY_LINE   1
+#define CMPT_FORMAT       2
+#define CMPT_BAD_FRAGMENT 3
+#define CMPT_BAD_POSITION 4
+
+typedef struct cmpt_result {
+    int64_t consumed;                           /* bytes of this piece that were taken */
+    int64_t n_lines;                            /* of the whole stream so far: lines read (a stopping line included), */
+    int64_t n_records, n_fragments, n_names;    /*   records, fragments and names */
+    int64_t stop_line;                          /* 1-based in the whole stream; 0 = no stop */
+    int64_t stop_offset, stop_len;              /* where the stopping line lies in the stream's bytes, without its newline */
+    int32_t stop_kind, pad_;                    /* CMPT_* */
+} cmpt_result;
+
+/* what the parse left on the device (device pointers; valid until the next cmpt_add or cmpt_begin on the context) */
+typedef struct cmpt_device {
+    const cmp_record* records;                  /* n_records */
+    const uint32_t*   frag_start;               /* n_fragments + 1, closed by n_records */
+    const uint8_t*    name_bytes;               /* the names one behind the other */
+    const int64_t*    name_off;                 /* n_names + 1 */
+    int64_t n_records, n_fragments, n_names, n_name_bytes;
+    int32_t device, pad_;
+} cmpt_device;
+
+typedef struct cmpt_print_result {
+    int64_t n_rows, text_bytes;
+    int64_t bad_row;                            /* the lowest row with a ref outside the dictionary, -1 if none */
+} cmpt_print_result;
+
+/* HIP-event times, summed over the pieces of a stream (parse) and of the latest print */
+typedef struct cmpt_timing {
+    float   upload_ms, tables_ms, lines_ms, names_ms, layout_ms;      /* parse */
+    float   lengths_ms, write_ms, download_ms;                         /* print: lengths + scan, write, cmpt_text_fetch */
+    int64_t text_bytes, out_bytes;
+    int32_t n_pieces, pad_;
+} cmpt_timing;
+
+typedef struct cmpt_ctx cmpt_ctx;
+/* max_names in [1, 2^28]: the name table is a power of two of at least twice it.  Fails without a GPU. */
+int  cmpt_create(int device, int64_t max_names, cmpt_ctx** out);
+void cmpt_destroy(cmpt_ctx* c);
+int  cmpt_begin(cmpt_ctx* c);
+int  cmpt_add(cmpt_ctx* c, const uint8_t* text, int64_t len, int32_t final, cmpt_result* result);
+/* the same for text in device memory (on the context's device; it is copied, and needs no padding) */
+int  cmpt_add_device(cmpt_ctx* c, const uint8_t* text_device, int64_t len, int32_t final, cmpt_result* result);
+int  cmpt_view(const cmpt_ctx* c, cmpt_device* out);
+/* records (room for n_records) and fragment starts (room for n_fragments + 1) to the host; NULL = not wanted;
+ * DSA_E_CAPACITY if a wanted buffer is short */
+int  cmpt_fetch(cmpt_ctx* c, cmp_record* records, int64_t record_cap, uint32_t* frag_start, int64_t frag_cap);
+/* the names' bytes and n_names + 1 offsets; NULL = not wanted; DSA_E_CAPACITY as above */
+int  cmpt_names_fetch(cmpt_ctx* c, uint8_t* bytes, int64_t byte_cap, int64_t* off, int64_t off_cap);
+/* The device-pointer twins of cmp_bin_upload_records and cmp_bin_upload_fragments: device-to-device copies into what
+ * cmp_bin_reserve reserved, from memory on the binner's device (a cmpt_view, for one).  Complete on return. */
+int  cmpt_bin_upload_records_device(cmp_binner* b, const cmp_record* records_device, int64_t n, int64_t at);
+int  cmpt_bin_upload_fragments_device(cmp_binner* b, const uint32_t* frag_start_device, int64_t n, int64_t at);
+/* The rows of the last cmp_problems_select where they are (valid until the next select on the object). */
+int  cmpt_problems_rows_view(cmp_problems* p, const cmp_row** rows_device, int64_t* n_rows);
+/* The lines of n_rows rows (host memory / memory of the context's device) into the context; n_rows = 0 is empty text. */
+int  cmpt_print_rows(cmpt_ctx* c, const cmp_row* rows, int64_t n_rows, cmpt_print_result* result);
+int  cmpt_print_rows_device(cmpt_ctx* c, const cmp_row* rows_device, int64_t n_rows, cmpt_print_result* result);
+/* The text of the last print.  *n_bytes always receives its size; DSA_E_CAPACITY if cap is short (nothing is copied). */
+int  cmpt_text_fetch(cmpt_ctx* c, uint8_t* buf, int64_t cap, int64_t* n_bytes);
+int  cmpt_get_timing(const cmpt_ctx* c, cmpt_timing* out);
+const char* cmpt_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

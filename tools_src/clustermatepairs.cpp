@@ -5,7 +5,8 @@
 // thread per fragment, a stable radix sort by bin-pair key in place of the reference's hash map); the per-bin-pair
 // filters and the output (:292-375,478-584) are host code; MatePairEM::DoClustering for all bin pairs runs on the
 // GPU in batches through include/defuse_mpe.h.  DEFUSE_CMP_DEVICE_PROBLEMS=1 (opt-in) moves the per-bin-pair filters and the choice
-// of the lines to print to the GPU as well (cmp_problems_* of include/defuse_cmp.h): no list leaves the device.  No CPU fallback: DEFUSE_CMP_HOST_BINNING=1 selects the host
+// of the lines to print to the GPU as well (cmp_problems_* of include/defuse_cmp.h): no list leaves the device.
+// DEFUSE_CMP_DEVICE_TEXT=1 (opt-in, implies it) also parses the alignment text and prints the cluster text there (cmpt_*).  No CPU fallback: DEFUSE_CMP_HOST_BINNING=1 selects the host
 // transcription of the bucketing as a cross-check (tests compare the two), it is never taken by itself.
 // Iteration orders the reference leaves to boost::unordered_map are the canonical ascending-key
 // orders of SURVEY.md 8(c).
@@ -235,12 +236,24 @@ int main(int argc, char* argv[])
     // The host stages below stay the default and the yardstick; they also serve the host cross-check of the binning, several
     // devices (the shares of mpe_cluster_batch_sharded take host arrays) and DEFUSE_CMP_DUMP_PROBLEMS (a dump of the host stages).
     bool device_problems = [] { const char* e = std::getenv("DEFUSE_CMP_DEVICE_PROBLEMS"); return e && std::atoi(e) != 0; }();
+    // DEFUSE_CMP_DEVICE_TEXT=1 (opt-in, implies the above): the alignment file goes to the device as text and is parsed there,
+    // the records reach the binner without leaving the device, and the rows of every output round are printed there and come
+    // down as the bytes of the cluster file (include/defuse_cmp.h, cmpt_*).  Where the device-problems path falls back, so does this.
+    bool device_text = [] { const char* e = std::getenv("DEFUSE_CMP_DEVICE_TEXT"); return e && std::atoi(e) != 0; }();
+    if (device_text) device_problems = true;
     auto keep_host_path = [&](const char* why) {
-        if (timing) std::cerr << "[clustermatepairs] DEFUSE_CMP_DEVICE_PROBLEMS: stays on the host path (" << why << ")" << std::endl;
-        device_problems = false;
+        if (timing)
+            std::cerr << "[clustermatepairs] " << (device_text ? "DEFUSE_CMP_DEVICE_TEXT" : "DEFUSE_CMP_DEVICE_PROBLEMS") << ": stays on the host path (" << why
+                      << ")" << std::endl;
+        device_problems = device_text = false;
     };
     if (device_problems && host_binning) keep_host_path("DEFUSE_CMP_HOST_BINNING=1");
     if (device_problems && std::getenv("DEFUSE_CMP_DUMP_PROBLEMS")) keep_host_path("DEFUSE_CMP_DUMP_PROBLEMS dumps the host stages");
+    if (device_text) {                                                        // (the default path asks this after the binning; the text has to know before)
+        std::vector<int> devs = devices_from_env();
+        std::sort(devs.begin(), devs.end());
+        if (std::unique(devs.begin(), devs.end()) - devs.begin() > 1) keep_host_path("DEFUSE_GPUS names more than one device");
+    }
     int gpu_device = -1;                                                      // the device of this process's first GPU call
     cmp_binner* binner = nullptr;
     int binner_rc = DSA_OK;
@@ -280,7 +293,7 @@ int main(int argc, char* argv[])
     };
     std::vector<size_t> cut(nThreads + 1, text.size());
     cut[0] = 0;
-    for (unsigned t = 1; t < nThreads; ++t) {
+    for (unsigned t = 1; t < nThreads && !device_text; ++t) {
         size_t pos = std::max(cut[t - 1], text.size() / nThreads * t);
         if (pos > 0 && pos < text.size() && text[pos - 1] != '\n') pos = line_end(pos);
         while (pos > 0 && pos < text.size()) {                // not inside a fragment: move on while the name repeats
@@ -364,9 +377,54 @@ int main(int argc, char* argv[])
             pc.recs.push_back(a);
         }
     };
-    run_threads(parse_piece);
-    if (timing) { std::cerr << "[clustermatepairs]   lines per piece:"; for (const Piece& pc : pieces) std::cerr << " " << pc.lines; std::cerr << std::endl; }
-    stage("  parsed");
+    // DEFUSE_CMP_DEVICE_TEXT: the same on the device, the mapped file in pieces of at most 1 GiB
+    cmpt_ctx* textCtx = nullptr;
+    cmpt_result parsed{};
+    auto text_failed = [&]() -> void { die(std::string("Error: alignment text on the GPU failed: ") + cmpt_last_error()); };
+    if (device_text) {
+        if (binner_thread.joinable()) binner_thread.join();
+        if (binner_rc != DSA_OK || !binner) die(std::string("Error: no usable MI355X/HIP device (") + binner_error + ")");
+        if (cmpt_create(gpu_device, (int64_t)1 << 20, &textCtx) != DSA_OK) text_failed();
+        const size_t pieceBytes = (size_t)1 << 30;
+        for (size_t pos = 0; pos < text.size() && parsed.stop_line == 0;) {
+            const size_t len = std::min(pieceBytes, text.size() - pos);
+            const bool last = pos + len == text.size();
+            if (cmpt_add(textCtx, (const uint8_t*)text.data() + pos, (int64_t)len, last ? 1 : 0, &parsed) != DSA_OK) text_failed();
+            if (!last && parsed.consumed == 0) die("Error: alignment text on the GPU failed: a line of more than 2^30 bytes");
+            pos += (size_t)parsed.consumed;
+        }
+        if (timing) {
+            cmpt_timing tt{};
+            cmpt_get_timing(textCtx, &tt);
+            std::cerr << "[clustermatepairs]   alignment text on the device: " << parsed.n_lines << " lines, " << parsed.n_records << " records, "
+                      << parsed.n_fragments << " fragments, " << parsed.n_names << " reference names in " << tt.n_pieces << " piece(s); upload " << tt.upload_ms
+                      << " ms, tables " << tt.tables_ms << " ms, lines " << tt.lines_ms << " ms, names " << tt.names_ms << " ms, layout " << tt.layout_ms << " ms"
+                      << std::endl;
+        }
+        stage("  parsed on the device");
+        if (parsed.stop_line) {                               // the tool's message, with the text it quotes taken from the mapped file
+            const char* line = text.data() + parsed.stop_offset;
+            const size_t len = (size_t)parsed.stop_len;
+            const std::string n = std::to_string(parsed.stop_line);
+            if (parsed.stop_kind == CMPT_EMPTY_LINE) die("Error: Empty alignment line " + n);
+            if (parsed.stop_kind == CMPT_FORMAT) die("Error: Format error for alignment line " + n);
+            if (parsed.stop_kind == CMPT_BAD_FRAGMENT) {
+                const char* tab = (const char*)memchr(line, '\t', len);
+                die("Error: bad integer '" + std::string(line, tab ? (size_t)(tab - line) : len) + "' as fragment name on line " + n);
+            }
+            const char* p = line;                             // CMPT_BAD_POSITION: from field 4 to the end of the line
+            for (int k = 0; k < 4 && p; ++k) {
+                p = (const char*)memchr(p, '\t', (size_t)(line + len - p));
+                if (p) ++p;
+            }
+            if (!p) p = line + len;
+            die("Error: bad integer '" + std::string(p, (size_t)(line + len - p)) + "' on line " + n);
+        }
+    } else {
+        run_threads(parse_piece);
+        if (timing) { std::cerr << "[clustermatepairs]   lines per piece:"; for (const Piece& pc : pieces) std::cerr << " " << pc.lines; std::cerr << std::endl; }
+        stage("  parsed");
+    }
     {
         size_t lineBase = 0;
         for (const Piece& pc : pieces) {                      // the first bad line of the file, as a serial reader meets it
@@ -552,9 +610,15 @@ int main(int argc, char* argv[])
         }
         if (binner_thread.joinable()) binner_thread.join();
         if (binner_rc != DSA_OK || !binner) die(std::string("Error: no usable MI355X/HIP device (") + binner_error + ")");
-        if (cmp_bin_reserve(binner, (int64_t)recBase[nThreads], (int64_t)fragBase[nThreads]) != DSA_OK) die(std::string("Error: ") + cmp_last_error());
         std::vector<int> rcs(nThreads, DSA_OK);
-        run_threads([&](unsigned t) {
+        if (device_text) {                                    // the parsed records are on the binner's device already
+            cmpt_device tv{};
+            if (cmpt_view(textCtx, &tv) != DSA_OK) text_failed();
+            if (cmp_bin_reserve(binner, tv.n_records, tv.n_fragments) != DSA_OK) die(std::string("Error: ") + cmp_last_error());
+            rcs[0] = cmpt_bin_upload_records_device(binner, tv.records, tv.n_records, 0);
+            if (rcs[0] == DSA_OK) rcs[0] = cmpt_bin_upload_fragments_device(binner, tv.frag_start, tv.n_fragments + 1, 0);
+        } else if (cmp_bin_reserve(binner, (int64_t)recBase[nThreads], (int64_t)fragBase[nThreads]) != DSA_OK) die(std::string("Error: ") + cmp_last_error());
+        if (!device_text) run_threads([&](unsigned t) {
             Piece& pc = pieces[t];
             rcs[t] = cmp_bin_upload_records(binner, pc.recs.data(), (int64_t)pc.recs.size(), (int64_t)recBase[t]);
             if (rcs[t] != DSA_OK) return;
@@ -570,9 +634,16 @@ int main(int argc, char* argv[])
         t_binned = now();
         if (st.err_record >= 0) {
             // the alignment on which the reference stops (:178-192 DebugChecks, :28-65 packing limits): its message and exit
-            unsigned t = 0;
-            while (t + 1 < nThreads && (size_t)st.err_record >= recBase[t + 1]) ++t;
-            const cmp_record& a = pieces[t].recs[(size_t)st.err_record - recBase[t]];
+            cmp_record a{};
+            if (device_text) {
+                std::vector<cmp_record> all((size_t)parsed.n_records);
+                if (cmpt_fetch(textCtx, all.data(), (int64_t)all.size(), nullptr, 0) != DSA_OK) text_failed();
+                a = all[(size_t)st.err_record];
+            } else {
+                unsigned t = 0;
+                while (t + 1 < nThreads && (size_t)st.err_record >= recBase[t + 1]) ++t;
+                a = pieces[t].recs[(size_t)st.err_record - recBase[t]];
+            }
             // (the first of its bins that stops, walked again here: the device names the record and the kind)
             const int startBin = (a.start - minFusionRange) / binLength, endBin = (a.end + minFusionRange) / binLength;
             std::vector<std::string> lines;
@@ -720,6 +791,8 @@ int main(int argc, char* argv[])
         // output (:549-583): the rows of a round of problems come down in print order; every host thread formats a contiguous share
         int clusterID = 0;
         std::vector<cmp_row> rows;
+        double printMs[3] = {0, 0, 0};                                          // DEFUSE_CMP_DEVICE_TEXT: lengths + scan, write, download
+        int64_t printedBytes = 0;
         auto write_range = [&](size_t cLo, size_t cHi) {
             for (size_t lo = cLo; lo < cHi;) {                   // rounds of about four million mate pairs bound the rows and the text held in memory
                 size_t hi = lo;
@@ -727,10 +800,27 @@ int main(int argc, char* argv[])
                 int64_t nRows = 0;
                 if (cmp_problems_select(probs, (int64_t)lo, (int64_t)hi, nClusters.data() + lo, view.member + probOff[lo], clusterID, &nRows) != DSA_OK)
                     die(std::string("Error: cluster rows on the GPU failed: ") + cmp_last_error());
-                rows.resize((size_t)nRows);
-                if (cmp_problems_rows(probs, rows.data(), nRows, &nRows) != DSA_OK) die(std::string("Error: cluster rows on the GPU failed: ") + cmp_last_error());
                 for (size_t p = lo; p < hi; ++p) clusterID += nClusters[p];
                 std::vector<std::string> texts(nThreads);
+                if (device_text) {                              // the rows are printed where they are; their text comes down
+                    const cmp_row* rowsDevice = nullptr;
+                    cmpt_print_result pr{};
+                    int64_t nBytes = 0;
+                    if (cmpt_problems_rows_view(probs, &rowsDevice, &nRows) != DSA_OK) die(std::string("Error: cluster rows on the GPU failed: ") + cmp_last_error());
+                    if (cmpt_print_rows_device(textCtx, rowsDevice, nRows, &pr) != DSA_OK) die(std::string("Error: cluster text on the GPU failed: ") + cmpt_last_error());
+                    texts[0].resize((size_t)pr.text_bytes);
+                    if (cmpt_text_fetch(textCtx, (uint8_t*)&texts[0][0], pr.text_bytes, &nBytes) != DSA_OK)
+                        die(std::string("Error: cluster text on the GPU failed: ") + cmpt_last_error());
+                    cmpt_timing tt{};
+                    cmpt_get_timing(textCtx, &tt);
+                    printMs[0] += tt.lengths_ms; printMs[1] += tt.write_ms; printMs[2] += tt.download_ms;
+                    printedBytes += nBytes;
+                    out.write_round_async(std::move(texts), nThreads);
+                    lo = hi;
+                    continue;
+                }
+                rows.resize((size_t)nRows);
+                if (cmp_problems_rows(probs, rows.data(), nRows, &nRows) != DSA_OK) die(std::string("Error: cluster rows on the GPU failed: ") + cmp_last_error());
                 run_threads([&](unsigned t) {
                     std::string& buf = texts[t];
                     auto put_int = [&](int v) {
@@ -780,6 +870,9 @@ int main(int argc, char* argv[])
                       << std::endl;
             std::cerr << "[clustermatepairs] " << nChunks << " chunk(s), stages overlapped: problems " << t_build << " s, clustering " << t_cluster
                       << " s, output " << t_write << " s" << std::endl;
+            if (device_text)
+                std::cerr << "[clustermatepairs]   cluster text on the device: " << printedBytes << " bytes; lengths + scan " << printMs[0] << " ms, write "
+                          << printMs[1] << " ms, download " << printMs[2] << " ms" << std::endl;
         }
         finish(clusterID);
     }
