@@ -93,7 +93,23 @@ constexpr uint32_t BIAS2 = 0x04000400u;
 constexpr uint32_t TWO2 = 0x00020002u;
 constexpr uint32_t FOUR2 = 0x00040004u;
 constexpr uint32_t SIX2 = 0x00060006u;
+constexpr uint32_t EIGHT2 = 0x00080008u;
 __host__ __device__ constexpr uint32_t drift2(int i) { return (uint32_t)(2 * i) * 0x00010001u; }
+// The table-driven sweeps and the table-driven replay keep column i of a tile in a frame of its own, X[i] = V + BIAS + d(i) per
+// field, so that the move from the left neighbour (V(i-1) - 2) is X[i-1] as it stands wherever d(i) = d(i-1) + 2.  The generic
+// kernels let d run over the whole tile (drift2).  Here it has period DRIFT_P: the move stays free inside a quad of columns,
+// the frame wraps once per quad (X[4q-1] - 8 enters column 4q, and the table term of column 4q carries d(4q) - d(4q-1) = -6),
+// and columns of equal residue share a frame, so that maxima and comparisons over a tile's columns need no per-column rebasing.
+// What is stored (bnd, cmax, rmax) has the drift removed and does not depend on d at all.
+//
+// Field range.  V >= 0 in every cell (a cell's own value of the row above is one of the three candidates), so X[i] >= BIAS16 +
+// d(i).  At a wrap column two candidates can fall below BIAS16, the smallest positive normal fp16 pattern: the left move
+// X[4q-1] - 8 >= BIAS16 - 2 and never the diagonal (X[4q-1] of the row above, >= BIAS16 + 6, plus a term >= -6).  Such a
+// candidate is a positive subnormal as fp16, or zero if the hardware flushes it, and in either case below the third operand of
+// the same max3, X[4q] of the row above >= BIAS16, a normal: it can never be the result, so the result is exact in both modes.
+// No field borrows from its neighbour either: BIAS16 - 2 > 0.
+constexpr int DRIFT_P = 4;
+__host__ __device__ constexpr uint32_t drift_of(int i) { return (uint32_t)(2 * (i % DRIFT_P)) * 0x00010001u; }
 
 typedef unsigned short v2u __attribute__((ext_vector_type(2)));
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
@@ -373,14 +389,24 @@ __device__ __forceinline__ void build_tables(uint32_t* __restrict__ T, int n_gro
             lo[k] = q0 == REF_PAD16 ? 0u : ((q0 >> 8) == cls_byte[k] ? 4u : 1u);
             hi[k] = (q1 == REF_PAD16 ? 0u : ((q1 >> 8) == cls_byte[k] ? 4u : 1u)) << 16;
         }
-        // +2 per field for i > 0: the diagonal move from column i-1 to i picks up the drift
-        const uint32_t drift = i > 0 ? TWO2 : 0u;
+        // The diagonal move from column i-1 to i picks up d(i) - d(i-1) per field (drift_of): +2 inside a quad, -6 where the
+        // frame wraps (i a multiple of DRIFT_P), nothing at column 0, whose diagonal comes from the drift-free boundary.
+        // A wrap column's terms are negative, -6 (padding), -5 or -2.  A table word is the exact 32-bit sum lo + (hi << 16) in
+        // two's complement, so that one v_add_u32 gives both fields exactly: the sweep adds it to fields >= BIAS16 + 6, the low
+        // field's sum stays in [BIAS16, 0xFFFF] once its carry is counted, and that carry is what the word's upper half is short of.
+        // Padded columns keep term 0 before the drift, as before: the values V of every cell are the same for any d, and with
+        // them the property that a padded column never exceeds the row maximum of the valid ones.
+        const int dd = i == 0 ? 0 : (i % DRIFT_P) != 0 ? 2 : 2 - 2 * DRIFT_P;
         if (SPLIT) {                   // rows 0..4: M1 term by M1 class, rows 5..9: M2 term by M2 class, 16 bits each
+            // v_perm joins the halves into (H << 16) | L.  At a wrap column L = lo - 6 is always negative, so as the low half of a
+            // 32-bit term it always carries into the upper half: H is stored as hi - 6 - 1.  The carry out of the whole word
+            // (the upper field's sum passes 2^16 as well) is dropped by the 32-bit add, which is the two's complement sum meant.
+            const int carry = dd < 0 ? 1 : 0;
             unsigned short* col = reinterpret_cast<unsigned short*>(T + gi * TGROUP_SPLIT) + i;
 #pragma unroll
             for (int k = 0; k < NCLS; ++k) {
-                col[k * TROW] = (unsigned short)(lo[k] + (drift & 0xFFFFu));
-                col[(NCLS + k) * TROW] = (unsigned short)((hi[k] + (drift & 0xFFFF0000u)) >> 16);
+                col[k * TROW] = (unsigned short)((int)lo[k] + dd);
+                col[(NCLS + k) * TROW] = (unsigned short)((int)(hi[k] >> 16) + dd - carry);
             }
         } else {
             uint32_t* col = T + gi * TGROUP + i;
@@ -388,7 +414,7 @@ __device__ __forceinline__ void build_tables(uint32_t* __restrict__ T, int n_gro
             for (int t = 0; t < NCOMBO; ++t) {
                 int k1, k2;
                 table_row_classes(t, k1, k2);
-                col[t * TROW] = (lo[k1] | hi[k2]) + drift;
+                col[t * TROW] = (lo[k1] | hi[k2]) + (uint32_t)dd * 0x00010001u;
             }
         }
     }
@@ -953,14 +979,17 @@ __device__ __forceinline__ HitCursor cursor_init(const KeptRow* __restrict__ kr,
 
 // Columns of the tile whose value at this row equals the given targets, both fields in one pass.  A target
 // is the row maximum (no column exceeds it) or NO_TARGET16 (above every value), so per column
-// sat(X - (target - 1 + drift)) is 1 exactly on a hit: one add (drift), one saturating packed subtract
-// and one shift-or into a hit-bit accumulator.
+// sat(X - (target - 1 + drift)) is 1 exactly on a hit: one saturating packed subtract and one shift-or into
+// a hit-bit accumulator (the comparands, one per frame of the drift, are formed once).
 constexpr uint32_t NO_TARGET16 = 0x7F00u;   // above BIAS16 + 4 * 7600 + drift, and + drift still fits the field
 template <int WT>
 __device__ __forceinline__ void equal_columns(const uint32_t (&X)[WT], uint32_t target2, uint64_t& m0, uint64_t& m1)
 {
     uint32_t hit[W / 16];                       // bits of the columns WT..W-1 stay 0
     const uint32_t below = target2 - 0x00010001u;
+    uint32_t below_d[DRIFT_P];                  // one comparand per frame (drift_of), not one per column
+#pragma unroll
+    for (int k = 0; k < DRIFT_P; ++k) below_d[k] = below + drift_of(k);
 #pragma unroll
     for (int q = 0; q < W / 16; ++q) {
         uint32_t acc = 0;
@@ -968,7 +997,7 @@ __device__ __forceinline__ void equal_columns(const uint32_t (&X)[WT], uint32_t 
         for (int k = 15; k >= 0; --k) {
             const int i = 16 * q + k;
             if (i >= WT) continue;
-            const uint32_t c = below + drift2(i);
+            const uint32_t c = below_d[i % DRIFT_P];
             typedef unsigned short us2 __attribute__((ext_vector_type(2)));
             const uint32_t y = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(us2, X[i]), __builtin_bit_cast(us2, c)));   // v_pk_sub_u16 clamp
             asm("v_lshl_or_b32 %0, %0, 1, %1" : "+v"(acc) : "v"(y));   // bit k: lo field hits, bit 16+k: hi field hits (left to
@@ -1106,7 +1135,7 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
 
     uint32_t X[WT];
 #pragma unroll
-    for (int i = 0; i < WT; ++i) X[i] = BIAS2 + drift2(i);
+    for (int i = 0; i < WT; ++i) X[i] = BIAS2 + drift_of(i);
     const uint4 bias4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint32_t bprev = BIAS2;
     const int ngq = (Rw >> 2) + 1;
@@ -1161,7 +1190,7 @@ __device__ __forceinline__ void replay_fast_wg(uint32_t* T, FinishLds* fl, const
                     an = X[4 * q + 3] + vn.x;
                     X[4 * q + 3] = max3(a, X[4 * q + 3], X[4 * q + 2]);
                     a = an;
-                    up = X[4 * q + 3];
+                    up = X[4 * q + 3] - EIGHT2;     // the frame wraps (drift_of)
                     v = vn;
                 }
                 record_hits(X, j, lq, kr, kc, n_kept, has0, has1, hc, masks, li.mask_begin);
@@ -1439,7 +1468,7 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
     (void)g; (void)tile;
     uint32_t X[NW];
 #pragma unroll
-    for (int i = 0; i < NW; ++i) X[i] = BIAS2 + drift2(i);
+    for (int i = 0; i < NW; ++i) X[i] = BIAS2 + drift_of(i);
     const uint4 bias4 = make_uint4(BIAS2, BIAS2, BIAS2, BIAS2);
     uint32_t bprev = BIAS2;
     const int ngq = (lq_max >> 2) + 1;
@@ -1487,7 +1516,7 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
                         an = X[4 * q + 3] + vn.x;
                         X[4 * q + 3] = max3(a, X[4 * q + 3], X[4 * q + 2]);
                         a = an;
-                        up = X[4 * q + 3];
+                        up = X[4 * q + 3] - EIGHT2;     // the frame wraps (drift_of)
                         v = vn;
                     }
                 } else {
@@ -1517,25 +1546,31 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
                         an = X[4 * q + 3] + vn.x;
                         X[4 * q + 3] = max3(a, X[4 * q + 3], X[4 * q + 2]);
                         a = an;
-                        up = X[4 * q + 3];
+                        up = X[4 * q + 3] - EIGHT2;     // the frame wraps (drift_of)
                     }
                 }
-                {   // the tile's row maximum: one max3 per two columns, two interleaved accumulators (padded columns have
-                    // substitution term 0 and never exceed the valid ones: no masking)
-                    uint32_t acc0 = BIAS2, acc1 = BIAS2;
+                {   // the tile's row maximum: one max3 per two columns.  Columns of equal residue share a frame (drift_of), so
+                    // each of the four accumulators takes its columns as they stand and only the accumulators are rebased
+                    // (padded columns have substitution term 0 and never exceed the valid ones: no masking)
+                    static_assert(DRIFT_P == 4, "one accumulator per column of a quad");
+                    uint32_t acc[4] = {BIAS2, BIAS2, BIAS2, BIAS2};      // V = 0 in frame 0: not above any column of any frame
 #pragma unroll
-                    for (int i = 0; i < NW; i += 4) {
-                        acc0 = max3(acc0, X[i] - drift2(i), X[i + 1] - drift2(i + 1));
-                        acc1 = max3(acc1, X[i + 2] - drift2(i + 2), X[i + 3] - drift2(i + 3));
+                    for (int i = 0; i + 8 <= NW; i += 8) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) acc[k] = max3(acc[k], X[i + k], X[i + 4 + k]);
                     }
-                    cmv[sidx] = max2(acc0, acc1);
+                    if constexpr (NW % 8 != 0) {                           // an odd number of quads: the last one alone
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) acc[k] = max2(acc[k], X[NW - 4 + k]);
+                    }
+                    cmv[sidx] = max2(max3(acc[0], acc[1] - TWO2, acc[2] - FOUR2), acc[3] - SIX2);
                 }
                 // alive: a field >= thr = 4j - slack (biased).  Both fields at once: x >= thr <=> max(x, thr-1) != thr-1;
                 // rows past the lane's read compare against 0xFFFF, which nothing exceeds (thr_of_row).
                 const uint32_t tm2 = thr_of_row(thr0, j, j <= lq_lane);
                 alive_bits |= pk_max_u16(cmv[sidx], tm2) ^ tm2;
                 if (!LAST) {
-                    bov[sidx] = X[NW - 1] - drift2(NW - 1);
+                    bov[sidx] = X[NW - 1] - drift_of(NW - 1);
                     if ((pk_max_u16(bov[sidx], tm2) ^ tm2) != 0u) last_bnd = j;
                 }
             }
@@ -1577,7 +1612,7 @@ __device__ __forceinline__ int sweep_tile_fast(const uint32_t* __restrict__ tb, 
                 n_gap_groups += g2 - (gq + 1);
                 if (!resume) { gq = g2; break; }                    // g2 groups are stored
 #pragma unroll
-                for (int i = 0; i < NW; ++i) X[i] = BIAS2 + drift2(i);
+                for (int i = 0; i < NW; ++i) X[i] = BIAS2 + drift_of(i);
                 bprev = in_prev;
                 b_n = bb;
                 rc_n = rows1[(int64_t)g2 * WAVE];
