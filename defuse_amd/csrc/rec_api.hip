@@ -225,6 +225,9 @@ int rec_sort_pass(rec_store* s, const uint64_t* key, int bits, uint32_t*& cur, u
 
 }  // namespace
 
+// for rect_api.hip, which must refuse a store of another device before it touches either (not part of the C ABI)
+__attribute__((visibility("hidden"))) int recstore_device(const rec_store* s) { return s->device; }
+
 extern "C" {
 
 const char* rec_last_error(void) { return g_rec_err.c_str(); }

@@ -84,6 +84,74 @@ int  rec_text(rec_store* s, const int64_t* kept, int64_t n_kept, char* out, int6
 int  rec_get_timing(const rec_store* s, rec_timing* out);
 const char* rec_last_error(void);
 
+/* ---- alignment text ---------------------------------------------------------------------------------------------------
+ * The way into a store for an alignment FILE (splitreads.alignments, what SplitAlignment::ReadSortedAlignments reads,
+ * tools/SplitAlignment.cpp:319-369): rect_add parses one piece of the text on the device and appends the records of its lines
+ * behind the store's last record.  Text up, rec_sort, rec_text down is `LC_ALL=C sort -n -k 1 FILE...` for files of plain
+ * lines (below), and for sorted inputs also `sort -m -n -k 1`: GNU sort's last-resort comparison makes its order total up to
+ * identical lines.
+ *
+ * Lines.  Only '\n' and '\t' are special; a '\r' belongs to the field it is in.  With final = 1 a last line without a newline
+ * is a line; with final = 0 it is not consumed (the caller gives it again in front of the next piece).  Empty text has no line.
+ *
+ * Per line, in this order:
+ *   1. Fewer than nine tab-separated fields: stop RECT_FEW_FIELDS, stop_field = -1.  An empty line has one field and stops
+ *      here.  (The reference tests "< 7" and then indexes [8]; the host parser of tools_src/evaluate.hpp stops below nine.)
+ *   2. Fields 0 to 8 are checked in order; the first failing field decides the stop kind, and stop_field is its index.
+ *      Field 3 must be exactly "0" or "1" (lexical_cast<bool>), else RECT_BAD_BOOL.  Every other field must be an integer,
+ *      else RECT_BAD_INTEGER: an optional '+' or '-', then digits only, at least one, and a value in the int range; leading
+ *      zeros are fine (field_int of tools_src/defuse_host.hpp).
+ *   3. Fields beyond the ninth are ignored.
+ *   4. The record is dsa_record{fusion_id, frag, read_end, revcomp, ref_first, ref_second, read_first, read_second, score,
+ *      pair_idx = 0} from fields 0 to 8.
+ *   5. A line is PLAIN if its bytes, without the newline, are exactly what rec_text prints for its record: nine "%d\t".
+ *      "+7", "007", "-0", a missing last tab, an extra field and a trailing '\r' all make a line parse but not be plain.
+ *      Lines that are not plain still give records; they are counted, because printing their records would not give their
+ *      bytes back and GNU sort's numeric key reads them differently.
+ *
+ * Stop.  A stop ends the stream, as the reference's exit(1) does: the lowest stopping line wins, the records of the lines
+ * before it are appended, and `consumed` ends in front of it.
+ *
+ * The conventions of this header hold.  Argument errors that can be told from the arguments alone are found before a device
+ * is touched.  len > 2^31 - 1 is DSA_E_LIMIT: the caller gives the text in pieces.  A store that would pass its record bound
+ * is DSA_E_LIMIT, and nothing is appended.  The ctx and the store must be on one device, else DSA_E_ARG.
+ */
+#define RECT_FEW_FIELDS  1            /* fewer than nine fields                                                          */
+#define RECT_BAD_INTEGER 2            /* a field other than the fourth is no int                                         */
+#define RECT_BAD_BOOL    3            /* the fourth field is not "0" or "1"                                              */
+
+typedef struct rect_result {
+    int64_t consumed;        /* bytes of the piece that are dealt with: up to the stopping line, else all whole lines     */
+    int64_t n_lines;         /* lines consumed (those in front of a stop)                                                 */
+    int64_t n_records;       /* records appended: one per consumed line                                                   */
+    int64_t stop_line;       /* 1-based within the call; 0 without a stop                                                 */
+    int64_t n_other;         /* lines among the consumed ones that are not plain                                          */
+    int64_t first_other;     /* 1-based line of the first of them; 0 if there is none                                     */
+    int32_t stop_kind;       /* RECT_FEW_FIELDS ... of the stopping line; 0 without a stop                                */
+    int32_t stop_field;      /* index of the field that stopped; -1 for RECT_FEW_FIELDS and without a stop                */
+    int32_t stop_id_read;    /* 1 if the stopping line has at least seven fields and field 0 is an integer: what
+                                ReadSortedAlignments' look-ahead has checked before it decides that a line opens the next
+                                group, so an evalsplitalign caller knows whether the running group is still evaluated     */
+    int32_t stop_id;         /* that integer; 0 without it                                                                */
+} rect_result;
+
+typedef struct rect_timing { /* HIP events, of the most recent rect_add                                                   */
+    float   upload_ms;       /* the text to the device                                                                    */
+    float   device_ms;       /* tables, the per-line kernel and the result                                                */
+    int64_t text_bytes;      /* bytes sent up (with final = 0: up to the last newline)                                    */
+    int64_t n_lines;
+    int64_t n_records;
+} rect_timing;
+
+typedef struct rect_ctx rect_ctx;     /* opaque: the text buffers and tables of one device; not for two threads at once */
+
+int  rect_create(int device, rect_ctx** out);
+void rect_destroy(rect_ctx* ctx);
+/* Parses text[0 .. len) and appends to `store` (whatever it holds stays, and keeps its place).  *result is always written. */
+int  rect_add(rect_ctx* ctx, rec_store* store, const uint8_t* text, int64_t len, int32_t final, rect_result* result);
+int  rect_get_timing(const rect_ctx* ctx, rect_timing* out);
+const char* rect_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,26 @@ def pipeline(out, n_chunks, stages, parallel=1, threads=16):
     return P("splitreads.break")
 
 
+def gpu_sort_row(out, n_chunks):
+    """After pipeline(): one `defuse_glue sort_alignments` over the unsorted chunk files, in place of the chain's sort stage;
+    its file must be the GNU-sorted one byte for byte."""
+    P = lambda n: os.path.join(out, n)
+    chunks = [P("split.%d" % c) for c in range(n_chunks)]
+    t0 = time.time()
+    r = subprocess.run([os.path.join(BIN, "defuse_glue"), "sort_alignments", "-o", P("g.alignments")] + chunks, capture_output=True, text=True,
+                       env=dict(os.environ, DEFUSE_TIMING="1"))
+    row = {"stage": "defuse_glue sort_alignments over %d chunks" % n_chunks, "wall_s": round(time.time() - t0, 3), "exit_status": r.returncode,
+           "replaces": "sort -n -k 1 per chunk + sort -m", "bytes_in": int(sum(os.path.getsize(c) for c in chunks)),
+           "timing": [l for l in r.stderr.splitlines() if l.startswith("[sort_alignments]")]}
+    if r.returncode != 0:
+        raise SystemExit("sort_alignments failed (%d): %s" % (r.returncode, r.stderr[-500:]))
+    row["same_file_as_gnu_sort"] = subprocess.call(["cmp", "-s", P("g.alignments"), P("splitreads.alignments")]) == 0
+    if not row["same_file_as_gnu_sort"]:
+        raise SystemExit("sort_alignments' file differs from the GNU-sorted one")
+    os.unlink(P("g.alignments"))
+    return row
+
+
 def fused_legs(out, n_chunks):
     """The back half of the chain (get_align_regions -> dosplitalign -> sort -> evalsplitalign) in dosplitalign's fused mode
     (DEFUSE_FUSED=1, SURVEY 8(f)-2), after pipeline() has run: (1) per chunk with --sorted (regions file as in the chain), so that GNU sort only merges;
@@ -408,6 +428,8 @@ def main():
     ap.add_argument("--check", action="store_true", help="small sizes: compare the final files with the oracle chain and time it (the CPU baseline)")
     ap.add_argument("--generate-only", action="store_true")
     ap.add_argument("--no-fused", dest="fused", action="store_false", help="skip the two fused-mode legs (DEFUSE_FUSED=1, SURVEY 8(f)-2)")
+    ap.add_argument("--gpu-sort", action="store_true", help="after the chain: one `defuse_glue sort_alignments` over the chunks' alignment files, timed and "
+                                                            "compared with the GNU-sorted file")
     args = ap.parse_args()
     info, planted, names = generate(args.out, args.fragments, chrom_len=args.chrom_len, chunk=args.chunk, lo=args.support[0], hi=args.support[1])
     info["fragments_per_fusion"] = args.support
@@ -444,6 +466,8 @@ def main():
         same = all(open(P("psplit.%d" % c), "rb").read() == open(P("split.%d" % c), "rb").read() for c in range(info["chunks"]))
         res["dosplitalign_chunks_in_parallel"] = {"at_a_time": args.parallel, "wall_s": round(time.time() - t1, 3), "all_ok": all(r == 0 for r in rcs),
                                                   "same_files_as_one_at_a_time": same}
+    if args.gpu_sort:
+        res["gpu_sort"] = gpu_sort_row(args.out, info["chunks"])
     if args.fused:
         res["fused"] = fused_legs(args.out, info["chunks"])
     if args.check:

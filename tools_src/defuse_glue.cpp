@@ -6,15 +6,19 @@
 //   defuse_glue remove_duplicates <min_size>        scripts/remove_duplicates.pl:11-104   (stdin -> stdout)
 //   defuse_glue filter_unmatched                    scripts/filter_unmatched.pl:16-50     (stdin -> stdout)
 //   defuse_glue divide_sam_chr_pairs -t <trans> -p <prefix>   scripts/divide_sam_chr_pairs.pl:9-177 (stdin -> files + list on stdout)
+//   defuse_glue sort_alignments [-o out] f1 f2 ...  the `sort -n -k 1` / `sort -m -n -k 1` of scripts/defuse_run.pl:528,533
 //
 // A symlink named after a script (merge_clusters.pl -> defuse_glue) selects the subcommand by its own name, so the
-// pipeline's `$scripts_directory/<script>.pl` can point at it unchanged.  Host text work only: nothing here has a
-// device part (the files are a few hundred MB and every step is one pass), it is here because these steps sit between
-// clustermatepairs, setcover and dosplitalign and were the slowest links once those ran on the GPU.
+// pipeline's `$scripts_directory/<script>.pl` can point at it unchanged.  The script steps are host text work only: they have
+// no device part (the files are a few hundred MB and every step is one pass), they are here because these steps sit between
+// clustermatepairs, setcover and dosplitalign and were the slowest links once those ran on the GPU.  sort_alignments is the
+// one step with a device part: the sort between dosplitalign and evalsplitalign, on the record store of include/defuse_rec.h.
 // Where a script's output order follows Perl's hash order (randomised per process), the canonical order of
 // SURVEY 8(c) is used: ascending numeric ids, chromosome names in string order.
 #include <chrono>
 
+#include "../include/defuse_dsa.h"
+#include "../include/defuse_rec.h"
 #include "defuse_host.hpp"
 
 using namespace defuse;
@@ -314,6 +318,131 @@ int divide_sam_chr_pairs(int argc, char** argv)
     return 0;
 }
 
+// `LC_ALL=C sort -n -k 1 FILE...` of alignment files (splitreads.alignments chunks; scripts/defuse_run.pl:528,533 sorts each
+// chunk and merges them) on the GPU: the text goes up in pieces (include/defuse_rec.h, "alignment text"), the record store
+// sorts and prints, the sorted text comes down.  Only files of plain lines are sorted, because only their records print as
+// their bytes: anything else is declined with status 3 and nothing written, so that a caller falls back to GNU sort
+// (`defuse_glue sort_alignments -o OUT FILES || LC_ALL=C sort ...`).  A library failure, no GPU included, is status 1.
+int sort_alignments(int argc, char** argv)
+{
+    const char* usage = "Usage: sort_alignments [-o out] alignments1 [alignments2 ...]\n";
+    std::string out_name;
+    std::vector<std::string> names;
+    for (int a = 0; a < argc; ++a) {
+        const std::string t = argv[a];
+        if (t == "-o" || t == "--output") {
+            if (a + 1 >= argc) { std::cerr << usage; return 1; }
+            out_name = argv[++a];
+        } else names.push_back(t);
+    }
+    if (names.empty()) { std::cerr << usage; return 1; }
+    const bool timing = std::getenv("DEFUSE_TIMING") != nullptr;
+    int64_t piece_bytes = (int64_t)1 << 30;
+    if (const char* pb = std::getenv("DEFUSE_SORT_PIECE_BYTES")) {
+        char* end = nullptr;
+        const long long v = strtoll(pb, &end, 10);
+        if (end == pb || *end || v < 1) die(std::string("Error: DEFUSE_SORT_PIECE_BYTES is not a positive number: ") + pb);
+        piece_bytes = std::min<long long>(v, INT32_MAX);
+    }
+    auto finish = [](int rc) {
+        std::cout.flush();
+        std::cerr.flush();
+        fflush(nullptr);
+        if (std::getenv("DEFUSE_FULL_EXIT")) exit(rc);      // under a profiler that writes its files at exit
+        _exit(rc);                                          // no teardown of a runtime whose work is done
+    };
+    // the output: opened only when there is something to write, so a declined or failed run leaves OUT as it was
+    auto write_out = [&](const char* p, size_t n) {
+        if (out_name.empty()) {
+            if (n && fwrite(p, 1, n, stdout) != n) die("Error: failed writing the sorted alignments");
+            return;
+        }
+        const int fd = open(out_name.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (fd < 0) die("Error: unable to write to " + out_name);
+        for (size_t done = 0; done < n;) {
+            const ssize_t w = write(fd, p + done, n - done);
+            if (w <= 0) die("Error: failed writing " + out_name);
+            done += (size_t)w;
+        }
+        if (close(fd) != 0) die("Error: failed writing " + out_name);
+    };
+    const double t0 = now();
+    std::vector<MappedText> files(names.size());
+    size_t total = 0;
+    for (size_t k = 0; k < names.size(); ++k) {
+        if (!files[k].try_load(names[k], false)) die("Error: Unable to open " + names[k]);
+        total += files[k].size();
+    }
+    const double t_map = now();
+    if (total == 0) {                                       // nothing to sort: no device is touched
+        write_out(nullptr, 0);
+        return 0;
+    }
+    auto lib_failed = [&](const char* what, const char* err) { std::cerr << "Error: sorting on the GPU failed: " << what << ": " << err << std::endl; finish(1); };
+    rect_ctx* ctx = nullptr;
+    rec_store* store = nullptr;
+    const int device = dsa_pick_device();
+    if (rect_create(device, &ctx) != 0) lib_failed("rect_create", rect_last_error());
+    if (rec_create(device, &store) != 0) lib_failed("rec_create", rec_last_error());
+    auto decline = [&](const std::string& name, int64_t line, const std::string& why) {
+        std::cerr << "sort_alignments: " << name << " line " << line << ": " << why << "; not sorted here, use LC_ALL=C sort -n -k 1" << std::endl;
+        finish(3);
+    };
+    double upload_ms = 0, device_ms = 0;
+    int64_t n_pieces = 0;
+    for (size_t k = 0; k < names.size(); ++k) {
+        const MappedText& text = files[k];
+        int64_t lines_before = 0;
+        for (size_t pos = 0; pos < text.size();) {
+            size_t hi = std::min(text.size(), pos + (size_t)piece_bytes);
+            rect_result res;
+            for (;;) {
+                if (rect_add(ctx, store, (const uint8_t*)text.data() + pos, (int64_t)(hi - pos), hi == text.size() ? 1 : 0, &res) != 0)
+                    lib_failed("rect_add", rect_last_error());
+                if (res.consumed > 0 || res.stop_line || hi == text.size()) break;
+                hi = text.line_end(hi);                     // a line longer than a piece goes up whole
+            }
+            ++n_pieces;
+            if (timing) {
+                rect_timing t;
+                if (rect_get_timing(ctx, &t) == 0) { upload_ms += t.upload_ms; device_ms += t.device_ms; }
+            }
+            if (res.n_other) decline(names[k], lines_before + res.first_other, "the line is not what its record prints as (nine \"%d\\t\")");
+            if (res.stop_line) {
+                const std::string field = std::to_string(res.stop_field + 1);
+                decline(names[k], lines_before + res.stop_line,
+                        res.stop_kind == RECT_FEW_FIELDS ? "fewer than nine fields"
+                        : res.stop_kind == RECT_BAD_BOOL ? "field " + field + " is not 0 or 1" : "field " + field + " is not an integer");
+            }
+            lines_before += res.n_lines;
+            pos += (size_t)res.consumed;
+        }
+    }
+    const double t_parse = now();
+    if (rec_sort(store) != 0) lib_failed("rec_sort", rec_last_error());
+    const double t_sort = now();
+    // plain lines print as their own bytes: the text is the input and one newline per file that lacks its last one
+    const int64_t cap = (int64_t)(total + names.size());
+    std::unique_ptr<char[]> sorted(new char[(size_t)cap]);
+    int64_t bytes = 0;
+    if (rec_text(store, nullptr, 0, sorted.get(), cap, &bytes) != 0) lib_failed("rec_text", rec_last_error());
+    const double t_text = now();
+    write_out(sorted.get(), (size_t)bytes);
+    const double t_write = now();
+    if (timing) {
+        rec_timing t{};
+        (void)rec_get_timing(store, &t);
+        std::cerr << "[sort_alignments] " << names.size() << " file(s), " << total << " bytes, " << t.n_records << " records in " << n_pieces
+                  << " piece(s): map " << t_map - t0 << " s, upload+parse " << t_parse - t_map << " s, sort " << t_sort - t_parse
+                  << " s, print+download " << t_text - t_sort << " s, write " << t_write - t_text << " s\n"
+                  << "[sort_alignments] device: upload " << upload_ms << " ms, tables+parse " << device_ms << " ms, keys " << t.keys_ms << " ms, sorts "
+                  << t.sort_ms << " ms (" << t.n_sorts << "), permute " << t.gather_ms << " ms, format " << t.format_ms << " ms, download " << t.download_ms
+                  << " ms" << std::endl;
+    }
+    finish(0);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[])
@@ -325,7 +454,7 @@ int main(int argc, char* argv[])
     int first = 1;
     if (prog == "defuse_glue") {
         if (argc < 2) {
-            std::cerr << "Usage: defuse_glue merge_clusters|get_align_regions|remove_duplicates|filter_unmatched|divide_sam_chr_pairs [args]\n";
+            std::cerr << "Usage: defuse_glue merge_clusters|get_align_regions|remove_duplicates|filter_unmatched|divide_sam_chr_pairs|sort_alignments [args]\n";
             return 1;
         }
         prog = argv[1];
@@ -337,6 +466,7 @@ int main(int argc, char* argv[])
         if (prog == "remove_duplicates") return remove_duplicates(argc - first, argv + first);
         if (prog == "filter_unmatched") return filter_unmatched();
         if (prog == "divide_sam_chr_pairs") return divide_sam_chr_pairs(argc - first, argv + first);
+        if (prog == "sort_alignments") return sort_alignments(argc - first, argv + first);
     } catch (const GlueError& g) {
         die(g.msg);
     }
