@@ -380,12 +380,18 @@ struct __attribute__((visibility("hidden"))) task_store {
 
 namespace {
 
-// everything of task_store_create on the device
-int build_store(task_store* s, const task_reference* ref, const task_exons* ex, const task_params& P, const task_pair* pairs, int64_t n)
+int open_store(task_store* s)
 {
     if (s->st.create(hipStreamNonBlocking) != hipSuccess) return TASK_FAIL(DSA_E_DEVICE, "cannot create a stream");
     for (auto& e : s->ev)
         if (e.create() != hipSuccess) return TASK_FAIL(DSA_E_DEVICE, "cannot create an event");
+    return DSA_OK;
+}
+
+// Everything of task_store_create on the device, behind the upload: `pairs` are n pairs in device memory, which the store's
+// stream may read (the caller has recorded ev[0] and ev[1] around whatever brought them there, if n > 0).
+int build_store(task_store* s, const task_reference* ref, const task_exons* ex, const task_params& P, const task_pair* pairs, int64_t n)
+{
     hipStream_t st = s->st;
     const int64_t E = 2 * n;
     // the stores have pointers, whatever n
@@ -405,7 +411,6 @@ int build_store(task_store* s, const task_reference* ref, const task_exons* ex, 
     }
     dsa_limits lim{};
     (void)dsa_get_limits(nullptr, &lim);
-    DeviceBuffer<task_pair> dpairs;
     DeviceBuffer<EndPlan> plan;
     DeviceBuffer<u64> wlen, rlen, gcount, woff, roff, goff;
     DeviceBuffer<Totals> tot;
@@ -413,9 +418,6 @@ int build_store(task_store* s, const task_reference* ref, const task_exons* ex, 
     DeviceBuffer<Seg> seg_win;
     DeviceBuffer<Seg64> seg_rem;
     DeviceBuffer<uint32_t> key, idx, skey, sidx;
-    TASK_HIP(hipEventRecord(s->ev[0], st));
-    if (const int rc = upload(dpairs, pairs, (size_t)n, st)) return rc;
-    TASK_HIP(hipEventRecord(s->ev[1], st));
     TASK_HIP(plan.reserve((size_t)E));
     for (auto* b : {&wlen, &rlen, &gcount, &woff, &roff, &goff}) TASK_HIP(b->reserve((size_t)E));
     TASK_HIP(tot.reserve(1));
@@ -423,11 +425,11 @@ int build_store(task_store* s, const task_reference* ref, const task_exons* ex, 
     TASK_HIP(hipMemcpyAsync(tot.p, &none, sizeof none, hipMemcpyHostToDevice, st));
     const ExonsView X = ex->view();
     // (1) plan
-    hipLaunchKernelGGL(k_task_plan, dim3(grid_of(E)), dim3(BLOCK), 0, st, (const task_pair*)dpairs.p, E, P, (const task_seq*)ref->seqs.p, X, lim.max_ref_len,
+    hipLaunchKernelGGL(k_task_plan, dim3(grid_of(E)), dim3(BLOCK), 0, st, pairs, E, P, (const task_seq*)ref->seqs.p, X, lim.max_ref_len,
                        plan.p, wlen.p, rlen.p, tot.p);
     TASK_HIP(hipEventRecord(s->ev[2], st));
     // (2) count
-    hipLaunchKernelGGL(k_task_regions<false>, dim3(grid_of(E * REGION_GROUP)), dim3(BLOCK), 0, st, (const EndPlan*)plan.p, E, X, (const task_pair*)dpairs.p,
+    hipLaunchKernelGGL(k_task_regions<false>, dim3(grid_of(E * REGION_GROUP)), dim3(BLOCK), 0, st, (const EndPlan*)plan.p, E, X, pairs,
                        gcount.p, (const u64*)nullptr, (cand_region*)nullptr, (int64_t)0);
     TASK_HIP(hipEventRecord(s->ev[3], st));
     // (3) offsets and totals, in 64 bits
@@ -457,13 +459,13 @@ int build_store(task_store* s, const task_reference* ref, const task_exons* ex, 
     TASK_HIP(hipMemsetAsync(s->windows.bytes.p + WB, 0, SRC_PAD, st));
     TASK_HIP(hipMemsetAsync(s->tasks.rem.p + RB, 0, SRC_PAD, st));
     // (4) emit
-    hipLaunchKernelGGL(k_task_regions<true>, dim3(grid_of(E * REGION_GROUP)), dim3(BLOCK), 0, st, (const EndPlan*)plan.p, E, X, (const task_pair*)dpairs.p,
+    hipLaunchKernelGGL(k_task_regions<true>, dim3(grid_of(E * REGION_GROUP)), dim3(BLOCK), 0, st, (const EndPlan*)plan.p, E, X, pairs,
                        (u64*)nullptr, (const u64*)goff.p, s->regions.p, (int64_t)NR);
     // (5) records, descriptors, gathers
     TASK_HIP(seg_win.reserve((size_t)E));
     TASK_HIP(seg_rem.reserve((size_t)E));
     for (auto* b : {&key, &idx, &skey, &sidx}) TASK_HIP(b->reserve((size_t)n));
-    hipLaunchKernelGGL(k_task_records, dim3(grid_of(n)), dim3(BLOCK), 0, st, (const task_pair*)dpairs.p, n, (const EndPlan*)plan.p, (const u64*)woff.p,
+    hipLaunchKernelGGL(k_task_records, dim3(grid_of(n)), dim3(BLOCK), 0, st, pairs, n, (const EndPlan*)plan.p, (const u64*)woff.p,
                        (const u64*)roff.p, (const u64*)goff.p, (const u64*)gcount.p, s->records.p, key.p, idx.p, seg_win.p, seg_rem.p);
     TASK_HIP(hipEventRecord(s->ev[5], st));
     hipLaunchKernelGGL((k_bat_gather<WINDOW_GROUP, true, Seg>), dim3(grid_of(E * WINDOW_GROUP)), dim3(BLOCK), 0, st, (const Seg*)seg_win.p, E,
@@ -593,7 +595,17 @@ int task_store_create(const task_reference* reference, const task_exons* exons, 
     s->device = reference->device;
     s->n = n;
     s->timing.n_tasks = n;
-    if (const int rc = build_store(s, reference, exons, *params, pairs, n)) {
+    DeviceBuffer<task_pair> dpairs;                 // (outlives the synchronise below)
+    auto build = [&]() -> int {
+        if (const int rc = open_store(s)) return rc;
+        if (n) {
+            TASK_HIP(hipEventRecord(s->ev[0], s->st));
+            if (const int rc = upload(dpairs, pairs, (size_t)n, s->st)) return rc;
+            TASK_HIP(hipEventRecord(s->ev[1], s->st));
+        }
+        return build_store(s, reference, exons, *params, dpairs.p, n);
+    };
+    if (const int rc = build()) {
         (void)hipStreamSynchronize(s->st);          // nothing of a refused call is in flight when it returns
         delete s;
         return rc;
@@ -654,3 +666,37 @@ int task_store_get_timing(const task_store* s, task_timing* out)
 }
 
 }  // extern "C"
+
+// task_store_create for pairs that are in device memory already (taskt_api.hip): the argument checks that need no pairs, then
+// the same build.  The pairs' own checks are the caller's; max_seq is the number of sequences their seq indices stay below.
+__attribute__((visibility("hidden"))) int taskstore_create_device(int device, const task_reference* reference, const task_exons* exons, const task_params* params,
+                                                                  const task_pair* pairs_device, int64_t n, int64_t max_seq, task_store** out)
+{
+    *out = nullptr;
+    if (const int rc = taskhost::check_params(params, g_task_err)) return rc;
+    if (!reference || !exons) return TASK_FAIL(DSA_E_ARG, "no %s", !reference ? "reference" : "exons");
+    if (reference->device != device || exons->device != device)
+        return TASK_FAIL(DSA_E_ARG, "the reference and the exons are on devices %d and %d, the pairs on %d", reference->device, exons->device, device);
+    if (max_seq > reference->n_seqs)
+        return TASK_FAIL(DSA_E_ARG, "the pairs' sequences are numbered below %lld, the reference has %lld", (long long)max_seq, (long long)reference->n_seqs);
+    TASK_HIP(hipSetDevice(device));
+    task_store* s = new task_store();
+    s->device = device;
+    s->n = n;
+    s->timing.n_tasks = n;
+    auto build = [&]() -> int {
+        if (const int rc = open_store(s)) return rc;
+        if (n) {
+            TASK_HIP(hipEventRecord(s->ev[0], s->st));
+            TASK_HIP(hipEventRecord(s->ev[1], s->st));
+        }
+        return build_store(s, reference, exons, *params, pairs_device, n);
+    };
+    if (const int rc = build()) {
+        (void)hipStreamSynchronize(s->st);
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return DSA_OK;
+}

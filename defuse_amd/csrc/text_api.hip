@@ -25,6 +25,7 @@
 #include "../../include/defuse_text.h"
 #include "bat_shared.hpp"
 #include "hip_host.hpp"
+#include "txt_names.hpp"
 #include "txt_shared.hpp"
 
 namespace {
@@ -44,35 +45,6 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int READ_GROUP = 16;                // lanes per sequence in the gather, as bat_api.hip
 constexpr uint8_t UNTOLD = 2;
 static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");
-
-// ---- names ------------------------------------------------------------------------------------------------------------
-
-struct NamesView {
-    const uint8_t* bytes;
-    const int64_t* off;         // n names in ascending byte order (a prefix comes first)
-    const int64_t* len;
-    const int32_t* index;       // the caller's number of each
-    int64_t n;
-};
-
-__host__ __device__ inline int compare_bytes(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb)
-{
-    const int64_t n = na < nb ? na : nb;
-    for (int64_t k = 0; k < n; ++k)
-        if (a[k] != b[k]) return a[k] < b[k] ? -1 : 1;
-    return na < nb ? -1 : na > nb ? 1 : 0;
-}
-
-__device__ inline int32_t find_name(const NamesView& nv, const uint8_t* __restrict__ f, int64_t n)
-{
-    int64_t lo = 0, hi = nv.n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (compare_bytes(nv.bytes + nv.off[mid], nv.len[mid], f, n) < 0) lo = mid + 1; else hi = mid;
-    }
-    if (lo < nv.n && compare_bytes(nv.bytes + nv.off[lo], nv.len[lo], f, n) == 0) return nv.index[lo];
-    return -1;
-}
 
 // ---- SAM --------------------------------------------------------------------------------------------------------------
 
@@ -252,14 +224,7 @@ __global__ void k_fq_emit(const FqRec* __restrict__ rec, const u64* __restrict__
 
 }  // namespace
 
-struct txt_names {
-    int device = -1;
-    int64_t n = 0;
-    DeviceBuffer<uint8_t> bytes;
-    DeviceBuffer<int64_t> off, len;
-    DeviceBuffer<int32_t> index;
-    NamesView view() const { return NamesView{bytes.p, off.p, len.p, index.p, n}; }
-};
+struct txt_names : NameTable {};
 
 struct txt_ctx {
     int device = -1;
@@ -440,50 +405,8 @@ int txt_names_create(int device, const uint8_t* name_bytes, int64_t name_bytes_l
 {
     if (!out) return TXT_FAIL(DSA_E_ARG, "txt_names_create: no output");
     *out = nullptr;
-    if (n_names < 0 || name_bytes_len < 0) return TXT_FAIL(DSA_E_ARG, "negative size (%lld names, %lld bytes)", (long long)n_names, (long long)name_bytes_len);
-    if (n_names > (int64_t)INT32_MAX) return TXT_FAIL(DSA_E_LIMIT, "more than 2^31 - 1 names");
-    if ((n_names && !name_off) || (name_bytes_len && !name_bytes)) return TXT_FAIL(DSA_E_ARG, "txt_names_create: null pointer with non-zero size");
-    for (int64_t k = 0; k < n_names; ++k) {
-        if (name_off[k] < 0 || name_off[k] > name_bytes_len) return TXT_FAIL(DSA_E_ARG, "name %lld: begins outside the %lld bytes given", (long long)k, (long long)name_bytes_len);
-        if (name_off[k + 1] < name_off[k]) return TXT_FAIL(DSA_E_ARG, "name %lld: its offsets do not ascend (reversed)", (long long)k);
-        if (name_off[k + 1] > name_bytes_len) return TXT_FAIL(DSA_E_ARG, "name %lld: ends outside the %lld bytes given", (long long)k, (long long)name_bytes_len);
-    }
-    std::vector<int32_t> order((size_t)n_names);
-    std::iota(order.begin(), order.end(), 0);
-    auto cmp = [&](int32_t a, int32_t b) {
-        return compare_bytes(name_bytes + name_off[a], name_off[a + 1] - name_off[a], name_bytes + name_off[b], name_off[b + 1] - name_off[b]);
-    };
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        const int c = cmp(a, b);
-        return c ? c < 0 : a < b;
-    });
-    for (int64_t s = 1; s < n_names; ++s)
-        if (cmp(order[(size_t)s - 1], order[(size_t)s]) == 0)
-            return TXT_FAIL(DSA_E_ARG, "names %d and %d are equal", order[(size_t)s - 1], order[(size_t)s]);
-    if (hiphost::check_device(device, &g_txt_err)) return DSA_E_DEVICE;
-    TXT_HIP(hipSetDevice(device));
-    std::vector<int64_t> off((size_t)n_names), len((size_t)n_names);
-    for (int64_t s = 0; s < n_names; ++s) {
-        off[(size_t)s] = name_off[order[(size_t)s]];
-        len[(size_t)s] = name_off[order[(size_t)s] + 1] - name_off[order[(size_t)s]];
-    }
     txt_names* nm = new txt_names();
-    nm->device = device;
-    nm->n = n_names;
-    auto build = [&]() -> int {
-        TXT_HIP(nm->bytes.reserve((size_t)name_bytes_len));
-        TXT_HIP(nm->off.reserve((size_t)n_names));
-        TXT_HIP(nm->len.reserve((size_t)n_names));
-        TXT_HIP(nm->index.reserve((size_t)n_names));
-        if (name_bytes_len) TXT_HIP(hipMemcpy(nm->bytes.p, name_bytes, (size_t)name_bytes_len, hipMemcpyHostToDevice));
-        if (n_names) {
-            TXT_HIP(hipMemcpy(nm->off.p, off.data(), (size_t)n_names * sizeof(int64_t), hipMemcpyHostToDevice));
-            TXT_HIP(hipMemcpy(nm->len.p, len.data(), (size_t)n_names * sizeof(int64_t), hipMemcpyHostToDevice));
-            TXT_HIP(hipMemcpy(nm->index.p, order.data(), (size_t)n_names * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        return DSA_OK;
-    };
-    if (const int rc = build()) {
+    if (const int rc = name_table_create(g_txt_err, "txt_names_create", device, name_bytes, name_bytes_len, name_off, n_names, nm)) {
         delete nm;
         return rc;
     }

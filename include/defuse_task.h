@@ -14,8 +14,10 @@
  * regions of every task are made on the device.  The store hands out a bat_windows and a pred_tasks that bat_assemble* and
  * pred_predict* read in place; no host copy of the windows is made and there is no second device copy of them.
  *
- * Strings stay with the caller, who resolves every name to a dense index once: sequences of the FASTA (task_seq), chromosomes
- * and transcripts of the exon table, and the reference numbering of cand_region.ref.
+ * task_store_create leaves the strings with the caller, who resolves every name to a dense index once: sequences of the
+ * FASTA (task_seq), chromosomes and transcripts of the exon table, and the reference numbering of cand_region.ref.  The
+ * section "region and exon text" at the end takes the regions file and the exon table as text instead and resolves the names
+ * on the device.
  *
  * FastaIndex::Get, exactly (start and length are its int& parameters):
  *   - length < 0: returns the empty string before the name is looked at; start and length stay as they are;
@@ -48,7 +50,7 @@
  * defuse_dsa.h).  There is no CPU path: creating an object fails with DSA_E_DEVICE without a GPU.  Argument errors that can
  * be told from the arguments alone are found before a device is touched.  One object must not be used from two threads at
  * once.  Out of scope: the tools (they keep host CreateTasks and the task cache), sharing bytes with la_genome, a
- * cand_table_create from device regions, reading FASTA / .fai / exon text, more than one GPU per chain.
+ * cand_table_create from device regions, reading FASTA / .fai, more than one GPU per chain.
  */
 #ifndef DEFUSE_TASK_H_
 #define DEFUSE_TASK_H_
@@ -198,6 +200,135 @@ int task_store_fetch(task_store* store, task_record* records, int64_t records_ca
 int task_store_get_timing(const task_store* store, task_timing* out);
 
 const char* task_last_error(void);
+
+/* ---- region and exon text ------------------------------------------------------------------------------------------------
+ *
+ * The regions file (ReadAlignRegionPairs, tools/Parsers.cpp:211-264) and the exon table (ExonRegions::Read,
+ * tools/ExonRegions.cpp:21-112) go up as text; the lines are split, the integers read, the names sorted and looked up and the
+ * pairs made on the device, where taskt_store_create hands them to the kernels of task_store_create.  The pairs never come
+ * down unless taskt_pairs_fetch asks for them.
+ *
+ * Text, both files: lines end at '\n'; only '\n' and '\t' are special, a '\r' belongs to its field; a last line without a
+ * newline is a line; empty text has no line.  An integer is what boost::lexical_cast<int> reads: an optional sign, digits
+ * only, inside int ("+007" and "7" are one value, "+", "" and 2147483648 are none).  A text of more than 2^31 - 1 bytes is
+ * DSA_E_LIMIT.  Names are compared byte by byte as unsigned bytes; nothing is hashed.
+ *
+ * A stop ends the stream where the reference's exit(1) does: the result names the first line in file order that has any
+ * cause (stop_line, 1-based; stop_off / stop_len, its bytes without the newline, so that the caller can print the reference's
+ * message), the cause and its field; the other counts of the result are those of the lines in front of it or zero, as said
+ * below.  The call returns DSA_OK.  After a stop the ctx holds no table of that kind, and the calls that need one return
+ * DSA_E_ARG.
+ *
+ * Exon table, per line, in this order:
+ *   (1) length 0 or fewer than six fields: skipped (counted in n_skipped);
+ *   (2) fields (4, 5), (6, 7), ... are exons: the reference's loop runs k = 5; k < n_fields; k += 2, so a last unpaired field
+ *       is never looked at.  The first member of a pair that is no integer stops (TASKT_EXON_BAD_INTEGER, "Failed to
+ *       interpret exon:"); "g\tt\tc\t+\t1\t" has six fields and stops on field 5;
+ *   (3) field 3 is "+" or "-", else TASKT_EXON_BAD_STRAND ("Error: Unable to intepret strand");
+ *   (4) limits of this library, where the reference reads on (kinds >= TASKT_LIBRARY_LIMIT): field 1 (the transcript) or
+ *       field 2 (the chromosome) longer than TASKT_MAX_NAME bytes is TASKT_EXON_LONG_NAME with that field; a transcript
+ *       name that an earlier transcript line has is TASKT_EXON_DUPLICATE (field 1) on the later line (the reference
+ *       overwrites its maps and keeps the old bins, which an index-based table cannot say).
+ * The table: transcripts are numbered in ascending byte order of field 1, a prefix first (what task_exons_create wants for
+ * the reference's output order); the exons stay in file order, those of a transcript side by side; chromosomes are numbered
+ * by first appearance.  chrom_ref[c] is the position of the chromosome's name in ref_names, name_ref the position of the
+ * bytes gene + "|" + transcript; a name ref_names does not have gets n_names + c, or n_names + n_chroms + t for transcript t
+ * (every region has a ref, and no SAM line can match an absent name).  DSA_E_LIMIT if those numbers leave int32.  The
+ * derived columns and the checks of the table itself are task_exons_create's, with its codes and messages.
+ *
+ * Regions file, per line, in this order:
+ *   (1) length 0 or fewer than five fields: skipped;
+ *   (2) fields 0 and 1 are integers, else TASKT_REGION_BAD_INTEGER with the field ("Failed to interpret region:");
+ *   (3) field 1 is 0 or 1, else TASKT_REGION_BAD_END ("Error: DebugCheck pairEnd == 0 || pairEnd == 1 failed");
+ *   (4) field 3 is "+" or "-", else TASKT_REGION_BAD_STRAND;
+ *   (5) a line of exactly five fields is TASKT_REGION_BAD_INTEGER on field 5; fields 4 and 5 are integers, else the same
+ *       with their field.  Further fields are ignored.
+ * The pairs: one per distinct id, ascending (as int); per (id, end) the last line of the file wins; an end no line gives is
+ * the default Location (empty name, strand 0, start 0, end 0).  Every end, the default one too, is resolved: seq is the
+ * position of the whole name in seq_names or -1; transcript the index of the second '|'-separated field if the name has at
+ * least two and the exon table has that transcript, else -1 ("g|t|x" gives t, "g|" the empty name); chrom the index of the
+ * whole name among the exon table's chromosomes or -1.
+ *
+ * seq_names: position = the task_seq index of the caller's task_reference.  ref_names: position = the cand_region.ref
+ * numbering the caller's SAM parse uses.  They may be one object.  One ctx must not be used from two threads at once. */
+
+#define TASKT_MAX_NAME            64
+#define TASKT_EXON_BAD_INTEGER    1
+#define TASKT_EXON_BAD_STRAND     2
+#define TASKT_REGION_BAD_INTEGER  3
+#define TASKT_REGION_BAD_END      4
+#define TASKT_REGION_BAD_STRAND   5
+#define TASKT_LIBRARY_LIMIT       16
+#define TASKT_EXON_LONG_NAME      16
+#define TASKT_EXON_DUPLICATE      17
+
+typedef struct taskt_result {
+    int64_t n_lines;                   /* lines of the text; with a stop, the lines in front of it                     */
+    int64_t n_skipped;                 /* of them skipped by rule (1); 0 with a stop                                   */
+    int64_t n_items;                   /* transcripts of the table / pairs of the regions file; 0 with a stop          */
+    int64_t n_exons;                   /* exon table only                                                              */
+    int64_t n_chroms;                  /* exon table only                                                              */
+    int64_t name_bytes;                /* exon table only: the bytes of all transcript names (field 1)                 */
+    int64_t stop_line;                 /* 1-based, 0: no stop                                                          */
+    int64_t stop_off, stop_len;        /* the stopping line is text[stop_off .. stop_off + stop_len)                   */
+    int32_t stop_kind;                 /* TASKT_*                                                                      */
+    int32_t stop_field;                /* the field that stopped, -1 without a stop                                    */
+} taskt_result;
+
+/* HIP-event times of the most recent call of each kind; exon_table_ms is the rest of taskt_parse_exons by a host clock. */
+typedef struct taskt_timing {
+    float   exon_upload_ms;            /* the exon text to the device                                                  */
+    float   exon_device_ms;            /* tables, line rules, exon emit, the two name sorts, the lookups               */
+    float   exon_table_ms;             /* the arrays down, task_exons_create, the call's allocations                   */
+    float   region_upload_ms;
+    float   region_device_ms;          /* tables, line rules, the sort by (id, end), the lookups, the pairs            */
+    float   check_ms;                  /* taskt_store_create: the pairs' checks (the rest is task_timing's)            */
+    int64_t exon_bytes;
+    int64_t region_bytes;
+} taskt_timing;
+
+typedef struct taskt_names taskt_names;         /* opaque: a list of names on one device               */
+typedef struct taskt_ctx taskt_ctx;             /* opaque: buffers, the exon table and the pairs       */
+
+/* Name k is name_bytes[name_off[k] .. name_off[k + 1]): name_off has n_names + 1 ascending entries.  The bytes are copied.
+ * DSA_E_ARG for offsets outside the bytes or descending, and for two equal names (naming both).  The contract of the text
+ * front's names table (defuse_text.h). */
+int taskt_names_create(int device, const uint8_t* name_bytes, int64_t name_bytes_len, const int64_t* name_off, int64_t n_names,
+                       taskt_names** out);
+void taskt_names_destroy(taskt_names* names);
+
+int taskt_create(int device, taskt_ctx** out);
+void taskt_destroy(taskt_ctx* ctx);
+
+/* The whole exon table (cdna.regions) as one text.  Replaces the ctx's exon table and drops its pairs.  ref_names may be
+ * destroyed once the call returns. */
+int taskt_parse_exons(taskt_ctx* ctx, const taskt_names* ref_names, const uint8_t* text, int64_t len, taskt_result* result);
+/* The whole regions file as one text.  DSA_E_ARG if the ctx has no exon table.  Replaces the ctx's pairs.  seq_names may be
+ * destroyed once the call returns. */
+int taskt_parse_regions(taskt_ctx* ctx, const taskt_names* seq_names, const uint8_t* text, int64_t len, taskt_result* result);
+
+/* What task_exons_create returns for the parsed table, owned by the ctx (never given to task_exons_destroy) and valid until
+ * the next taskt_parse_exons or taskt_destroy; NULL if there is none. */
+const task_exons* taskt_exons(const taskt_ctx* ctx);
+/* The parsed table: transcripts[t] and chrom_ref as task_exons_create took them, the exons in file order, and the name of
+ * transcript t as name_bytes[name_off[t] .. name_off[t + 1]) (name_off has n_items + 1 entries).  A part whose buffer is NULL
+ * (with capacity 0) is left out; DSA_E_CAPACITY if a part that is asked for does not fit (the result of taskt_parse_exons
+ * says what is needed).  Capacities are in elements. */
+int taskt_exons_fetch(taskt_ctx* ctx, task_transcript* transcripts, int64_t transcripts_cap, task_exon* exons, int64_t exons_cap, int32_t* chrom_ref,
+                      int64_t chrom_cap, int64_t* name_off, int64_t name_off_cap, uint8_t* name_bytes, int64_t name_bytes_cap);
+/* The pairs, for tests and callers who want them; lines[2 * k + e], if given, is the 1-based line that gave pair k its end e,
+ * 0 for a default end. */
+int taskt_pairs_fetch(taskt_ctx* ctx, task_pair* pairs, int64_t pairs_cap, int64_t* lines, int64_t lines_cap);
+
+/* task_store_create over the ctx's exon table and pairs, which stay on the device: a task_store, used and destroyed through
+ * the store functions above.  seq_names of the regions parse must not have more names than the reference has sequences
+ * (DSA_E_ARG).  The pairs' checks are made on the device and name the lowest offending pair by index, fusion id and line:
+ * DSA_E_ARG for a negative fusion id, DSA_E_LIMIT for a coordinate beyond TASK_MAX_COORD, a span beyond TASK_MAX_REGION and
+ * more than 2^30 - 1 pairs. */
+int taskt_store_create(taskt_ctx* ctx, const task_reference* reference, const task_params* params, task_store** out);
+
+int taskt_get_timing(const taskt_ctx* ctx, taskt_timing* out);
+const char* taskt_last_error(void);
 
 #ifdef __cplusplus
 }

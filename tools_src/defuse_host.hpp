@@ -1227,6 +1227,12 @@ public:
         return true;
     }
     bool IsTranscript(const std::string& t) const { return gene_.count(t) != 0; }
+    // every transcript of the table, in no particular order: f(transcript, gene, chromosome, strand, exons)
+    template <class F>
+    void ForEachTranscript(F f) const
+    {
+        for (const auto& kv : gene_) f(kv.first, kv.second, chromosome_.at(kv.first), strand_.at(kv.first), exons_.at(kv.first));
+    }
     // GetGenes (:126-129): the reference lists its unordered_set of gene names; canonical order = ascending
     std::vector<std::string> GetGenes() const
     {
