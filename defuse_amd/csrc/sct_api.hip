@@ -321,6 +321,7 @@ struct sct_ctx {
     DeviceBuffer<int32_t, GrowSize> owner;
     DeviceBuffer<uint8_t, GrowSize> out;
     int64_t out_bytes = 0, owner_n = 0;
+    bool has_out = false;       // a cover has run on the pieces as they are: out[0, out_bytes) is its text
 };
 
 namespace {
@@ -581,6 +582,7 @@ int sct_begin(sct_ctx* c)
     c->pieces.clear();
     c->n_lines = c->n_bytes = 0;
     c->out_bytes = c->owner_n = 0;
+    c->has_out = false;
     c->timing = sct_timing{};
     return DSA_OK;
 }
@@ -597,6 +599,7 @@ int sct_add(sct_ctx* c, const uint8_t* text, int64_t len, int32_t final, int64_t
     if (!final) len = whole_lines(text, len);
     if (len == 0) return DSA_OK;
     c->out_bytes = c->owner_n = 0;                              // the last cover's results are of another input
+    c->has_out = false;
     const int rc = add_piece(c, text, len);
     if (rc != DSA_OK) (void)hipStreamSynchronize(c->st);        // nothing of a refused call is in flight when it returns
     else *consumed = len;
@@ -609,6 +612,7 @@ int sct_cover(sct_ctx* c, int64_t min_cluster_size, sct_result* r)
     *r = sct_result{};
     if (!c) return SCT_FAIL(DSA_E_ARG, "sct_cover: no ctx");
     c->out_bytes = c->owner_n = 0;
+    c->has_out = false;
     c->timing.parse_ms = c->timing.layout_ms = c->timing.cover_ms = c->timing.select_ms = c->timing.gather_ms = c->timing.download_ms = 0.f;
     c->timing.gather_bytes = c->timing.n_runs = 0;
     c->timing.n_components = c->timing.n_large = c->timing.cc_iterations = 0;
@@ -617,7 +621,7 @@ int sct_cover(sct_ctx* c, int64_t min_cluster_size, sct_result* r)
         (void)hipStreamSynchronize(c->st);
         c->out_bytes = c->owner_n = 0;
         *r = sct_result{};
-    }
+    } else c->has_out = r->status == SCT_OK || r->status == SCT_WRITE_STOP;
     return rc;
 }
 
@@ -662,3 +666,13 @@ int sct_get_timing(const sct_ctx* c, sct_timing* out)
 }
 
 }  // extern "C"
+
+// taskc_api.hip: where the last cover's output lies (no public header has this).  False if there is none.
+__attribute__((visibility("hidden"))) bool sct_cover_output_device(const sct_ctx* c, int* device, const uint8_t** text, int64_t* len)
+{
+    if (!c || !c->has_out) return false;
+    *device = c->device;
+    *text = c->out.p;
+    *len = c->out_bytes;
+    return true;
+}

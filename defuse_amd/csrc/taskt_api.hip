@@ -489,8 +489,10 @@ void drop_exons(taskt_ctx* c)
     c->n_pairs = 0;
 }
 
-// The text (len > 0) into `text` with its padding, and its line and tab tables; leaves c->L and c->n_lines.
-int load_text(taskt_ctx* c, DeviceBuffer<uint8_t, GrowSize>& text, const uint8_t* host, int64_t len, hipEvent_t start, hipEvent_t up)
+// The text (len > 0) into `text` with its padding, and its line and tab tables; leaves c->L and c->n_lines.  `kind` says
+// where `host` points: host memory, or memory of the ctx's device whose writer has finished.
+int load_text(taskt_ctx* c, DeviceBuffer<uint8_t, GrowSize>& text, const uint8_t* host, int64_t len, hipEvent_t start, hipEvent_t up,
+              hipMemcpyKind kind = hipMemcpyHostToDevice)
 {
     hipStream_t st = c->st;
     const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
@@ -501,7 +503,7 @@ int load_text(taskt_ctx* c, DeviceBuffer<uint8_t, GrowSize>& text, const uint8_t
     TASKT_HIP(c->totals.reserve(1));
     TASKT_HIP(c->out.reserve(1));
     TASKT_HIP(hipEventRecord(start, st));
-    TASKT_HIP(hipMemcpyAsync(text.p, host, (size_t)len, hipMemcpyHostToDevice, st));
+    TASKT_HIP(hipMemcpyAsync(text.p, host, (size_t)len, kind, st));
     TASKT_HIP(hipMemsetAsync(text.p + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
     TASKT_HIP(hipEventRecord(up, st));
     const uint4* chunks = reinterpret_cast<const uint4*>(text.p);
@@ -691,10 +693,10 @@ Resolver resolver(const taskt_ctx* c, const taskt_names* seqs)
                     SortedNames{c->etext.p, c->grp_off.p, c->grp_len.p, c->grp_cid.p, c->n_chroms}};
 }
 
-int parse_regions(taskt_ctx* c, const taskt_names* seqs, const uint8_t* text, int64_t len, taskt_result* result)
+int parse_regions(taskt_ctx* c, const taskt_names* seqs, const uint8_t* text, int64_t len, hipMemcpyKind kind, taskt_result* result)
 {
     hipStream_t st = c->st;
-    if (const int rc = load_text(c, c->rtext, text, len, c->ev[3], c->ev[4])) return rc;
+    if (const int rc = load_text(c, c->rtext, text, len, c->ev[3], c->ev[4], kind)) return rc;
     const Lines L = c->L;
     const int64_t n_lines = c->n_lines;
     TASKT_HIP(c->lines.reserve((size_t)n_lines));
@@ -844,7 +846,11 @@ int taskt_parse_exons(taskt_ctx* c, const taskt_names* ref_names, const uint8_t*
     return DSA_OK;
 }
 
-int taskt_parse_regions(taskt_ctx* c, const taskt_names* seq_names, const uint8_t* text, int64_t len, taskt_result* result)
+}  // extern "C"
+
+// taskt_parse_regions, and for taskc_api.hip the same over a text that lies in the memory of the ctx's device and whose writer
+// has finished (no public header has this one; the message is taskt_last_error's).
+static int parse_regions_from(taskt_ctx* c, const taskt_names* seq_names, const uint8_t* text, int64_t len, hipMemcpyKind kind, taskt_result* result)
 {
     if (const int rc = check_text("taskt_parse_regions", c, seq_names, text, len, result)) return rc;
     if (c->device != seq_names->device) return TASKT_FAIL(DSA_E_ARG, "taskt_parse_regions: ctx and names are on devices %d and %d", c->device, seq_names->device);
@@ -861,7 +867,7 @@ int taskt_parse_regions(taskt_ctx* c, const taskt_names* seq_names, const uint8_
         c->n_seq_names = seq_names->n;
         return DSA_OK;
     }
-    const int rc = parse_regions(c, seq_names, text, len, result);
+    const int rc = parse_regions(c, seq_names, text, len, kind, result);
     if (rc != DSA_OK) {
         (void)hipStreamSynchronize(c->st);
         c->has_pairs = false;
@@ -870,6 +876,20 @@ int taskt_parse_regions(taskt_ctx* c, const taskt_names* seq_names, const uint8_
     c->timing.region_upload_ms = hiphost::elapsed(c->ev[3], c->ev[4]);
     c->timing.region_device_ms = result->stop_line ? 0.f : hiphost::elapsed(c->ev[4], c->ev[5]);
     return DSA_OK;
+}
+
+__attribute__((visibility("hidden"))) int taskt_regions_from_device(taskt_ctx* c, const taskt_names* seq_names, int device, const uint8_t* text, int64_t len,
+                                                                    taskt_result* result)
+{
+    if (c && c->device != device) return TASKT_FAIL(DSA_E_ARG, "taskt_parse_regions: the text is on device %d, the ctx on %d", device, c->device);
+    return parse_regions_from(c, seq_names, text, len, hipMemcpyDeviceToDevice, result);
+}
+
+extern "C" {
+
+int taskt_parse_regions(taskt_ctx* c, const taskt_names* seq_names, const uint8_t* text, int64_t len, taskt_result* result)
+{
+    return parse_regions_from(c, seq_names, text, len, hipMemcpyHostToDevice, result);
 }
 
 const task_exons* taskt_exons(const taskt_ctx* c) { return c ? c->exons : nullptr; }

@@ -61,6 +61,7 @@
 #include "defuse_cand.h"
 #include "defuse_dsa.h"
 #include "defuse_pred.h"
+#include "defuse_sc.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -329,6 +330,111 @@ int taskt_store_create(taskt_ctx* ctx, const task_reference* reference, const ta
 
 int taskt_get_timing(const taskt_ctx* ctx, taskt_timing* out);
 const char* taskt_last_error(void);
+
+/* ---- cluster text ------------------------------------------------------------------------------------------------------
+ *
+ * The two steps between the set cover and the regions parse, on cluster text that is in device memory or goes there in
+ * pieces: what `defuse_glue remove_duplicates MIN` prints (scripts/remove_duplicates.pl), what `defuse_glue
+ * get_align_regions` prints (scripts/get_align_regions.pl), and the pairs of a taskt_ctx made from that regions text where
+ * it lies.  The text comes down only if taskc_fetch asks for it.
+ *
+ * Text: lines end at '\n'; a '\r' belongs to its field; a last line without a newline is a line; empty text has no line.
+ * Only the first eight tab-separated fields matter: cluster id, cluster end, fragment, read end, name, strand, start, end.
+ * Field 7 ends at the eighth tab or at the line's end; later fields are ignored.  An integer is an optional sign and digits
+ * only, inside int ("7", "+7" and "007" are one value).
+ *
+ * Dedup, per line, in this order:
+ *   (1) fewer than eight fields: TASKC_FEW_FIELDS (an empty line is one);
+ *   (2) fields 0, 1 and 2 are integers, else TASKC_BAD_INTEGER with the first such field;
+ *   (3) a cluster end other than 0 or 1: the line belongs to its run (it can begin, continue or separate runs) but carries no
+ *       fragment, and nothing more of it is checked;
+ *   (4) the position field is 6 if field 5 is exactly "+", else 7; it is an integer, else TASKC_BAD_INTEGER with that field.
+ *       The other of the two is never looked at.
+ * Dedup, per run (a maximal sequence of adjacent lines whose field 0 has one int value; an id that comes back later is a new
+ * run): per (fragment, cluster end) the last line in file order wins; a fragment with only one of its ends is
+ * TASKC_MISSING_END, attributed to the run's last line, stop_value the lowest such fragment; the fragments are ordered by
+ * (position of end 0, position of end 1, fragment) as int and the first of every distinct position pair is kept; the run is
+ * printed iff the kept fragments number at least min_cluster_size (a signed 64-bit compare: 0 or less keeps every run).
+ * Output: runs in file order, kept fragments ascending, per fragment the winning end-0 line, then the winning end-1 line,
+ * each the input's bytes and '\n'.
+ *
+ * Regions, per line: fewer than eight fields is TASKC_FEW_FIELDS; fields 0, 1, 6 and 7 are integers, checked in that order,
+ * else TASKC_BAD_INTEGER with the field.  Groups are (id, cluster end) over the whole text, any int as cluster end: name and
+ * strand are the bytes of fields 4 and 5 of the group's last line, start the least field 6, end the greatest field 7.  If no
+ * line stops, every id has exactly two distinct cluster ends, else TASKC_NOT_TWO_ENDS with stop_line 0 and stop_value the
+ * lowest such id.  Output: ids ascending, cluster ends ascending within an id, "id \t end \t name \t strand \t start \t end
+ * \n" with the integers in plain decimal.
+ *
+ * A stop ends the call as in the section above: it returns DSA_OK, the result names the lowest stopping line (1-based over
+ * all pieces, or over the dedup text for TASKC_DEDUP), its bytes, the cause, its field and stop_value; a line's own stop beats
+ * a run's on the same line; n_lines is that of the whole text and every other count is 0.  After a stop the ctx holds no
+ * output of that kind, and the calls that need one return DSA_E_ARG.
+ * One corner: the one-pass host tool reports a malformed field 0-2 on the line right behind a run before that run's missing
+ * end; here the run in front of such a line is complete, and its missing end, on the lower line, is what is reported.  (A
+ * line whose position field is malformed belongs to its run, so its own stop is never behind that run's.)
+ * One ctx must not be used from two threads at once. */
+
+#define TASKC_FEW_FIELDS    1
+#define TASKC_BAD_INTEGER   2
+#define TASKC_MISSING_END   3
+#define TASKC_NOT_TWO_ENDS  4
+#define TASKC_INPUT         0      /* source of taskc_regions: the text as added                                      */
+#define TASKC_DEDUP         1      /* source: the output of the last taskc_dedup; taskc_fetch: that text              */
+#define TASKC_REGIONS       2      /* taskc_fetch: the regions text of the last taskc_regions                         */
+
+typedef struct taskc_result {
+    int64_t n_lines;                   /* lines of the source text                                                     */
+    int64_t n_runs;                    /* dedup: runs                                                                  */
+    int64_t n_clusters;                /* regions: distinct ids                                                        */
+    int64_t n_fragments;               /* dedup: fragments of all runs                                                 */
+    int64_t n_kept_fragments;          /* dedup: fragments printed (two lines each)                                    */
+    int64_t n_kept_runs;               /* dedup: runs that passed min_cluster_size                                     */
+    int64_t out_bytes;                 /* bytes of the text made                                                       */
+    int64_t stop_line;                 /* 1-based, 0: no stop or TASKC_NOT_TWO_ENDS                                    */
+    int64_t stop_off, stop_len;        /* the stopping line is text[stop_off .. stop_off + stop_len) of the source     */
+    int64_t stop_value;                /* TASKC_MISSING_END: the fragment; TASKC_NOT_TWO_ENDS: the id                  */
+    int32_t stop_kind;                 /* TASKC_*, 0: no stop                                                          */
+    int32_t stop_field;                /* the field that stopped, else -1                                              */
+} taskc_result;
+
+/* HIP-event times: upload and tables summed over the pieces since taskc_begin, the others of the most recent call. */
+typedef struct taskc_timing {
+    float   upload_ms;                 /* the pieces to the device (or the cover's output copied)                      */
+    float   tables_ms;                 /* newline tables, line starts                                                  */
+    float   parse_ms;                  /* the line rule, once per input                                                */
+    float   sorts_ms;                  /* dedup: run heads, the sorts by (run, fragment) and (run, pos0, pos1)         */
+    float   select_ms;                 /* dedup: winners, duplicates, counts per run, output lengths and offsets       */
+    float   gather_ms;                 /* dedup: the kept lines copied                                                 */
+    float   regions_ms;                /* regions: keys, sort, min / max / last per group, the ends of every id        */
+    float   print_ms;                  /* regions: lengths, offsets, the text                                          */
+    int64_t text_bytes;
+    int64_t n_pieces;
+} taskc_timing;
+
+typedef struct taskc_ctx taskc_ctx;             /* opaque: the text, its lines and the two outputs     */
+
+int taskc_create(int device, taskc_ctx** out);
+void taskc_destroy(taskc_ctx* ctx);
+/* Forgets the text and both outputs. */
+int taskc_begin(taskc_ctx* ctx);
+/* One piece from host memory.  final = 0: only whole lines are consumed (*consumed says how many bytes; give the rest again
+ * in front of the next piece); final = 1: the piece's last line may lack its newline.  DSA_E_LIMIT for a piece of more than
+ * 2^31 - 1 bytes or more than 2^31 - 1 lines in all.  Drops both outputs. */
+int taskc_add(taskc_ctx* ctx, const uint8_t* text, int64_t len, int32_t final, int64_t* consumed);
+/* The output of cover's last sct_cover as one piece, copied from device memory to device memory; cover may be reused or
+ * destroyed afterwards.  DSA_E_ARG if it has no output or lives on another device. */
+int taskc_add_cover(taskc_ctx* ctx, const sct_ctx* cover);
+int taskc_dedup(taskc_ctx* ctx, int64_t min_cluster_size, taskc_result* result);
+/* source: TASKC_INPUT or TASKC_DEDUP (DSA_E_ARG if there is no dedup text). */
+int taskc_regions(taskc_ctx* ctx, int32_t source, taskc_result* result);
+/* len bytes from offset of the dedup text (which = TASKC_DEDUP) or the regions text (TASKC_REGIONS) to the host. */
+int taskc_fetch(taskc_ctx* ctx, int32_t which, int64_t offset, uint8_t* buf, int64_t len);
+/* Everything taskt_parse_regions does, with the regions text of the last taskc_regions read where it lies: `into` (same
+ * device, with an exon table) then holds the pairs for taskt_pairs_fetch and taskt_store_create.  Codes and the result are
+ * taskt_parse_regions'. */
+int taskc_parse_regions(taskc_ctx* ctx, taskt_ctx* into, const taskt_names* seq_names, taskt_result* result);
+int taskc_get_timing(const taskc_ctx* ctx, taskc_timing* out);
+const char* taskc_last_error(void);
 
 #ifdef __cplusplus
 }

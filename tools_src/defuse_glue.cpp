@@ -7,18 +7,21 @@
 //   defuse_glue filter_unmatched                    scripts/filter_unmatched.pl:16-50     (stdin -> stdout)
 //   defuse_glue divide_sam_chr_pairs -t <trans> -p <prefix>   scripts/divide_sam_chr_pairs.pl:9-177 (stdin -> files + list on stdout)
 //   defuse_glue sort_alignments [-o out] f1 f2 ...  the `sort -n -k 1` / `sort -m -n -k 1` of scripts/defuse_run.pl:528,533
+//   defuse_glue cluster_regions <min_size> -c clusters_out -r regions_out [clusters]   remove_duplicates, then get_align_regions
 //
 // A symlink named after a script (merge_clusters.pl -> defuse_glue) selects the subcommand by its own name, so the
-// pipeline's `$scripts_directory/<script>.pl` can point at it unchanged.  The script steps are host text work only: they have
-// no device part (the files are a few hundred MB and every step is one pass), they are here because these steps sit between
-// clustermatepairs, setcover and dosplitalign and were the slowest links once those ran on the GPU.  sort_alignments is the
-// one step with a device part: the sort between dosplitalign and evalsplitalign, on the record store of include/defuse_rec.h.
+// pipeline's `$scripts_directory/<script>.pl` can point at it unchanged.  The script steps are host text work (the files are a
+// few hundred MB and every step is one pass), they are here because these steps sit between clustermatepairs, setcover and
+// dosplitalign and were the slowest links once those ran on the GPU.  Two steps have a device part: sort_alignments, the sort
+// between dosplitalign and evalsplitalign on the record store of include/defuse_rec.h, and cluster_regions, which does
+// remove_duplicates and get_align_regions in one process on the cluster text section of include/defuse_task.h.
 // Where a script's output order follows Perl's hash order (randomised per process), the canonical order of
 // SURVEY 8(c) is used: ascending numeric ids, chromosome names in string order.
 #include <chrono>
 
 #include "../include/defuse_dsa.h"
 #include "../include/defuse_rec.h"
+#include "../include/defuse_task.h"
 #include "defuse_host.hpp"
 
 using namespace defuse;
@@ -443,6 +446,112 @@ int sort_alignments(int argc, char** argv)
     return 0;
 }
 
+// remove_duplicates and get_align_regions in one process on the GPU (include/defuse_task.h, "cluster text"): the cluster file
+// goes up in pieces, CLUSTERS_OUT is what `remove_duplicates MIN` prints and REGIONS_OUT what `get_align_regions` prints of
+// it.  Anything either host step would die of is declined with status 3 and neither file touched, so that a caller falls
+// back (`defuse_glue cluster_regions MIN -c C -r R FILE || { the two host steps; }`) and gets the host's message.  A library
+// failure, no GPU included, is status 1 with nothing written.
+int cluster_regions(int argc, char** argv)
+{
+    const char* usage = "Usage: cluster_regions min_cluster_size -c clusters_out -r regions_out [clusters]\n";
+    std::string clusters_out, regions_out, in_name = "-";
+    std::vector<std::string> plain;
+    for (int a = 0; a < argc; ++a) {
+        const std::string t = argv[a];
+        if ((t == "-c" || t == "-r") && a + 1 >= argc) { std::cerr << usage; return 1; }
+        if (t == "-c") clusters_out = argv[++a];
+        else if (t == "-r") regions_out = argv[++a];
+        else plain.push_back(t);
+    }
+    int min_size = 0;
+    if (plain.empty() || plain.size() > 2 || clusters_out.empty() || regions_out.empty() || !field_int(plain[0].data(), plain[0].size(), min_size)) {
+        std::cerr << usage;
+        return 1;
+    }
+    if (plain.size() == 2) in_name = plain[1];
+    const bool timing = std::getenv("DEFUSE_TIMING") != nullptr;
+    int64_t piece_bytes = (int64_t)1 << 30;
+    if (const char* pb = std::getenv("DEFUSE_GLUE_PIECE_BYTES")) {
+        char* end = nullptr;
+        const long long v = strtoll(pb, &end, 10);
+        if (end == pb || *end || v < 1) die(std::string("Error: DEFUSE_GLUE_PIECE_BYTES is not a positive number: ") + pb);
+        piece_bytes = std::min<long long>(v, INT32_MAX);
+    }
+    auto finish = [](int rc) {
+        std::cout.flush();
+        std::cerr.flush();
+        fflush(nullptr);
+        if (std::getenv("DEFUSE_FULL_EXIT")) exit(rc);      // under a profiler that writes its files at exit
+        _exit(rc);                                          // no teardown of a runtime whose work is done
+    };
+    auto lib_failed = [&](const char* what, const char* err) { std::cerr << "Error: cluster_regions on the GPU failed: " << what << ": " << err << std::endl; finish(1); };
+    const double t0 = now();
+    MappedText text;
+    if (!text.try_load(in_name, true, false)) die("Error: Unable to open clusters file " + in_name);
+    const double t_map = now();
+    taskc_ctx* ctx = nullptr;
+    if (taskc_create(dsa_pick_device(), &ctx) != 0) lib_failed("taskc_create", taskc_last_error());
+    if (taskc_begin(ctx) != 0) lib_failed("taskc_begin", taskc_last_error());
+    for (size_t pos = 0; pos < text.size();) {
+        size_t hi = std::min(text.size(), pos + (size_t)piece_bytes);
+        int64_t consumed = 0;
+        for (;;) {
+            if (taskc_add(ctx, (const uint8_t*)text.data() + pos, (int64_t)(hi - pos), hi == text.size() ? 1 : 0, &consumed) != 0)
+                lib_failed("taskc_add", taskc_last_error());
+            if (consumed > 0 || hi == text.size()) break;
+            hi = text.line_end(hi);                         // a line longer than a piece goes up whole
+        }
+        pos += (size_t)consumed;
+    }
+    const double t_up = now();
+    auto decline = [&](const char* step, const taskc_result& r) {
+        std::cerr << "cluster_regions: " << step;
+        if (r.stop_line) std::cerr << " line " << r.stop_line;
+        if (r.stop_kind == TASKC_FEW_FIELDS) std::cerr << ": fewer than eight fields";
+        else if (r.stop_kind == TASKC_BAD_INTEGER) std::cerr << ": field " << r.stop_field + 1 << " is not an integer";
+        else if (r.stop_kind == TASKC_MISSING_END) std::cerr << ": fragment " << r.stop_value << " of the cluster that ends here lacks a cluster end";
+        else std::cerr << ": cluster " << r.stop_value << " does not have two ends";
+        std::cerr << "; nothing written, use remove_duplicates and get_align_regions" << std::endl;
+        finish(3);
+    };
+    taskc_result dres, rres;
+    if (taskc_dedup(ctx, (int64_t)min_size, &dres) != 0) lib_failed("taskc_dedup", taskc_last_error());
+    if (dres.stop_kind) decline("clusters", dres);
+    if (taskc_regions(ctx, TASKC_DEDUP, &rres) != 0) lib_failed("taskc_regions", taskc_last_error());
+    if (rres.stop_kind) decline("kept clusters", rres);
+    const double t_dev = now();
+    std::unique_ptr<uint8_t[]> clusters(new uint8_t[(size_t)dres.out_bytes + 1]), regions(new uint8_t[(size_t)rres.out_bytes + 1]);
+    if (taskc_fetch(ctx, TASKC_DEDUP, 0, clusters.get(), dres.out_bytes) != 0) lib_failed("taskc_fetch", taskc_last_error());
+    if (taskc_fetch(ctx, TASKC_REGIONS, 0, regions.get(), rres.out_bytes) != 0) lib_failed("taskc_fetch", taskc_last_error());
+    const double t_down = now();
+    auto write_file = [&](const std::string& name, const uint8_t* p, size_t n) {
+        const int fd = open(name.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (fd < 0) die("Error: unable to write to " + name);
+        for (size_t done = 0; done < n;) {
+            const ssize_t w = write(fd, p + done, n - done);
+            if (w <= 0) die("Error: failed writing " + name);
+            done += (size_t)w;
+        }
+        if (close(fd) != 0) die("Error: failed writing " + name);
+    };
+    write_file(clusters_out, clusters.get(), (size_t)dres.out_bytes);
+    write_file(regions_out, regions.get(), (size_t)rres.out_bytes);
+    const double t_write = now();
+    if (timing) {
+        taskc_timing t{};
+        (void)taskc_get_timing(ctx, &t);
+        std::cerr << "[cluster_regions] " << text.size() << " bytes, " << dres.n_lines << " lines in " << t.n_pieces << " piece(s), " << dres.n_runs << " runs, "
+                  << dres.n_fragments << " fragments (" << dres.n_kept_fragments << " kept), " << rres.n_clusters << " clusters: map " << t_map - t0
+                  << " s, create+upload " << t_up - t_map << " s, dedup+regions " << t_dev - t_up << " s, download " << t_down - t_dev << " s, write "
+                  << t_write - t_down << " s\n"
+                  << "[cluster_regions] device: upload " << t.upload_ms << " ms, tables " << t.tables_ms << " ms, parse " << t.parse_ms << " ms, sorts " << t.sorts_ms
+                  << " ms, select " << t.select_ms << " ms, gather " << t.gather_ms << " ms, regions " << t.regions_ms << " ms, print " << t.print_ms << " ms"
+                  << std::endl;
+    }
+    finish(0);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[])
@@ -454,7 +563,7 @@ int main(int argc, char* argv[])
     int first = 1;
     if (prog == "defuse_glue") {
         if (argc < 2) {
-            std::cerr << "Usage: defuse_glue merge_clusters|get_align_regions|remove_duplicates|filter_unmatched|divide_sam_chr_pairs|sort_alignments [args]\n";
+            std::cerr << "Usage: defuse_glue merge_clusters|get_align_regions|remove_duplicates|filter_unmatched|divide_sam_chr_pairs|sort_alignments|cluster_regions [args]\n";
             return 1;
         }
         prog = argv[1];
@@ -467,6 +576,7 @@ int main(int argc, char* argv[])
         if (prog == "filter_unmatched") return filter_unmatched();
         if (prog == "divide_sam_chr_pairs") return divide_sam_chr_pairs(argc - first, argv + first);
         if (prog == "sort_alignments") return sort_alignments(argc - first, argv + first);
+        if (prog == "cluster_regions") return cluster_regions(argc - first, argv + first);
     } catch (const GlueError& g) {
         die(g.msg);
     }
