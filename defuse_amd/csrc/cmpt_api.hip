@@ -41,13 +41,14 @@ namespace {
 using hiphost::DeviceBuffer;
 using hiphost::GrowSize;
 using hiphost::grid_of;
+using hiphost::grow_keep;
+using hiphost::Keep;
 
 thread_local std::string g_cmpt_err;
 
 #define CMPT_HIP(call) HIPHOST_TRY(g_cmpt_err, call)
 #define CMPT_FAIL(code, ...) hiphost::fail(g_cmpt_err, code, __VA_ARGS__)
 
-constexpr size_t TEXT_PAD = 2 * CHUNK;        // zeroed: the last chunk is whole
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;       // a slot nobody has claimed
 constexpr uint32_t KNOWN = 0x80000000u;       // slot: a name of an earlier piece, its index below; per line: the same instead of a slot
@@ -68,9 +69,6 @@ struct Dict {
     const int64_t* off;         // n + 1
     int64_t n;
 };
-
-__device__ inline int64_t first_tab_rank(const Lines& L, int64_t i) { return i == 0 ? 0 : (int64_t)L.nl_tab[i - 1]; }
-__device__ inline int64_t end_tab_rank(const Lines& L, int64_t i) { return i < L.n_nl ? (int64_t)L.nl_tab[i] : L.n_tab; }
 
 // where field 0 of line i ends: at its first tab, or at the line's end
 __device__ inline int64_t field0_end(const Lines& L, int64_t i)
@@ -211,10 +209,6 @@ __global__ __launch_bounds__(BLOCK) void k_cmpt_rank(Lines L, int64_t n_valid, c
     new_len[g] = len;
 }
 
-struct Widen {
-    __host__ __device__ u64 operator()(uint32_t v) const { return (u64)v; }
-};
-
 // The first line of a new name appends it: index = names before this piece + rank, bytes behind those that are there.
 __global__ __launch_bounds__(BLOCK) void k_cmpt_assign(Lines L, int64_t n_valid, const uint32_t* __restrict__ where, const uint32_t* __restrict__ is_new,
                                                        const uint32_t* __restrict__ rank, const u64* __restrict__ byte_off, int64_t n_old, int64_t bytes_old,
@@ -298,19 +292,6 @@ __global__ __launch_bounds__(BLOCK) void k_cmpt_write(const cmp_row* __restrict_
     o += rec_write_field(r.end[ce], o, '\n');
 }
 
-// keeps the first `used` elements when the buffer has to grow
-template <typename T>
-hipError_t grow_keep(DeviceBuffer<T>& b, size_t used, size_t need, hipStream_t st)
-{
-    if (b.p && need <= b.cap) return hipSuccess;
-    DeviceBuffer<T> nb;
-    hipError_t e = nb.reserve(need + need / 2 + 64);
-    if (e == hipSuccess && used) e = hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) b.swap(nb);
-    return e;
-}
-
 }  // namespace
 
 struct cmpt_ctx {
@@ -330,10 +311,11 @@ struct cmpt_ctx {
     DeviceBuffer<int64_t> name_off;
     DeviceBuffer<uint32_t> slot, first;
     // a piece
-    DeviceBuffer<uint8_t, GrowSize> text, tmp, kind_of;
-    DeviceBuffer<u64, GrowSize> blk, blk_off, byte_off;
-    DeviceBuffer<Totals> totals;
-    DeviceBuffer<uint32_t, GrowSize> nl_pos, nl_tab, tab_pos, starts, frag_rank, where, is_new, new_len, rank;
+    DeviceBuffer<uint8_t, GrowSize> text, kind_of;
+    TextScratch scratch;
+    TextTables tables;
+    DeviceBuffer<u64, GrowSize> byte_off;
+    DeviceBuffer<uint32_t, GrowSize> starts, frag_rank, where, is_new, new_len, rank;
     DeviceBuffer<Summary> summary;
     // the printer
     DeviceBuffer<cmp_row, GrowSize> rows;
@@ -345,12 +327,6 @@ struct cmpt_ctx {
 };
 
 namespace {
-
-int64_t whole_lines(const uint8_t* text, int64_t len)
-{
-    const void* nl = len ? memrchr(text, '\n', (size_t)len) : nullptr;
-    return nl ? (int64_t)((const uint8_t*)nl - text) + 1 : 0;
-}
 
 int reset_stream(cmpt_ctx* c)
 {
@@ -379,40 +355,22 @@ int add_piece(cmpt_ctx* c, const uint8_t* text, int64_t len, bool on_device, boo
 {
     CMPT_HIP(hipSetDevice(c->device));
     hipStream_t st = c->st;
-    const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
-    const int64_t n_blocks = (n_chunks + BLOCK - 1) / BLOCK;
-    CMPT_HIP(c->text.reserve((size_t)(n_chunks * CHUNK) + TEXT_PAD));
-    CMPT_HIP(c->blk.reserve((size_t)n_blocks));
-    CMPT_HIP(c->blk_off.reserve((size_t)n_blocks));
-    CMPT_HIP(c->totals.reserve(1));
+    CMPT_HIP(c->text.reserve(padded_size(len)));
     CMPT_HIP(c->summary.reserve(1));
-    CMPT_HIP(hipEventRecord(c->ev[0], st));
-    CMPT_HIP(hipMemcpyAsync(c->text.p, text, (size_t)len, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    CMPT_HIP(hipMemsetAsync(c->text.p + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
-    CMPT_HIP(hipEventRecord(c->ev[1], st));
-    const uint4* chunks = reinterpret_cast<const uint4*>(c->text.p);
-    hipLaunchKernelGGL(k_txt_count<true>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, c->blk.p);
-    CMPT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->blk.p, c->blk_off.p, (int)n_blocks, st); }));
-    hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(64), 0, st, (const u64*)c->blk.p, (const u64*)c->blk_off.p, n_blocks, (const uint8_t*)c->text.p, len,
-                       c->totals.p);
     Totals tot{};
-    CMPT_HIP(hipMemcpyAsync(&tot, c->totals.p, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    CMPT_HIP(hipStreamSynchronize(st));
-    CMPT_HIP(hipGetLastError());
-    const int64_t n_nl = (int64_t)tot.n_nl, n_tab = (int64_t)tot.n_tab;
-    if (n_nl > len || n_tab > len) return CMPT_FAIL(DSA_E_DEVICE, "internal: %lld newlines and %lld tabs in %lld bytes", (long long)n_nl, (long long)n_tab, (long long)len);
+    if (const int rc = text_upload_count<true>(g_cmpt_err, c->scratch, c->text.p, text, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, len, c->ev[0],
+                                               c->ev[1], st, tot))
+        return rc;
+    const int64_t n_nl = (int64_t)tot.n_nl;
     const bool open_end = tot.last != '\n';
     const int64_t n_lines = n_nl + (open_end && final ? 1 : 0);
-    CMPT_HIP(c->nl_pos.reserve((size_t)n_nl));
-    CMPT_HIP(c->nl_tab.reserve((size_t)n_nl));
-    CMPT_HIP(c->tab_pos.reserve((size_t)n_tab));
-    hipLaunchKernelGGL(k_txt_tables<true>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, (const u64*)c->blk_off.p, n_nl, n_tab, c->nl_pos.p,
-                       c->nl_tab.p, c->tab_pos.p);
+    CMPT_HIP(c->tables.reserve(tot));
+    const Lines L = c->tables.place<true>(c->scratch, c->text.p, len, tot, st);
     CMPT_HIP(hipEventRecord(c->ev[2], st));
     *consumed = len;
     if (open_end && !final) {                                   // (the device form only)
         uint32_t last_nl = 0;
-        if (n_nl) CMPT_HIP(hipMemcpyAsync(&last_nl, c->nl_pos.p + (n_nl - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (n_nl) CMPT_HIP(hipMemcpyAsync(&last_nl, c->tables.nl_pos.p + (n_nl - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         CMPT_HIP(hipStreamSynchronize(st));
         *consumed = n_nl ? (int64_t)last_nl + 1 : 0;
     }
@@ -426,13 +384,12 @@ int add_piece(cmpt_ctx* c, const uint8_t* text, int64_t len, bool on_device, boo
         c->n_bytes += *consumed;
         return DSA_OK;
     }
-    const Lines L{c->text.p, c->nl_pos.p, c->nl_tab.p, c->tab_pos.p, len, n_nl, n_tab};
     const int64_t rec_base = c->res.n_records, frag_base = c->res.n_fragments, n_old = c->res.n_names, bytes_old = c->n_name_bytes;
     const unsigned gl = grid_of(n_lines + 1);
 
     // lines (the records of all lines of the piece have room: a stop is not known yet)
     if (rec_base + n_lines > MAX_RECORDS) return CMPT_FAIL(DSA_E_LIMIT, "more than 2^32 - 1 alignment records");
-    CMPT_HIP(grow_keep(c->recs, (size_t)rec_base, (size_t)(rec_base + n_lines), st));
+    CMPT_HIP(grow_keep(c->recs, Keep{(size_t)rec_base}, (size_t)(rec_base + n_lines), st));
     CMPT_HIP(c->kind_of.reserve((size_t)n_lines + 1));
     for (auto* b : {&c->starts, &c->frag_rank, &c->where, &c->is_new, &c->new_len, &c->rank}) CMPT_HIP(b->reserve((size_t)n_lines + 1));
     CMPT_HIP(c->byte_off.reserve((size_t)n_lines + 1));
@@ -459,7 +416,7 @@ int add_piece(cmpt_ctx* c, const uint8_t* text, int64_t len, bool on_device, boo
         // layout, first half: the fragments' ranks
         CMPT_HIP(hipEventRecord(c->ev[4], st));
         CMPT_HIP(hipMemsetAsync(c->starts.p + n_valid, 0, sizeof(uint32_t), st));
-        CMPT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        CMPT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceScan::ExclusiveSum(w, wb, c->starts.p, c->frag_rank.p, (int)(n_valid + 1), st);
         }));
         CMPT_HIP(hipEventRecord(c->ev[5], st));
@@ -468,11 +425,11 @@ int add_piece(cmpt_ctx* c, const uint8_t* text, int64_t len, bool on_device, boo
         hipLaunchKernelGGL(k_cmpt_probe, dim3(gv), dim3(BLOCK), 0, st, L, n_valid, D, c->slot.p, c->first.p, c->table_size - 1, c->where.p, c->summary.p);
         hipLaunchKernelGGL(k_cmpt_rank, dim3(gv), dim3(BLOCK), 0, st, L, n_valid, (const uint32_t*)c->where.p, (const uint32_t*)c->first.p, c->is_new.p,
                            c->new_len.p);
-        CMPT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        CMPT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceScan::ExclusiveSum(w, wb, c->is_new.p, c->rank.p, (int)(n_valid + 1), st);
         }));
         hipcub::TransformInputIterator<u64, Widen, const uint32_t*> lengths(c->new_len.p, Widen());
-        CMPT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        CMPT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceScan::ExclusiveSum(w, wb, lengths, c->byte_off.p, (int)(n_valid + 1), st);
         }));
         CMPT_HIP(hipEventRecord(c->ev[6], st));
@@ -492,9 +449,9 @@ int add_piece(cmpt_ctx* c, const uint8_t* text, int64_t len, bool on_device, boo
         if (n_new_frags > n_valid || n_new > n_valid || bytes_new > len)
             return CMPT_FAIL(DSA_E_DEVICE, "internal: %lld fragments, %lld names of %lld bytes in %lld lines", (long long)n_new_frags, (long long)n_new,
                              (long long)bytes_new, (long long)n_valid);
-        CMPT_HIP(grow_keep(c->name_bytes, (size_t)bytes_old, (size_t)(bytes_old + bytes_new), st));
-        CMPT_HIP(grow_keep(c->name_off, (size_t)n_old + 1, (size_t)(n_old + n_new + 1), st));
-        CMPT_HIP(grow_keep(c->frag_start, (size_t)frag_base + 1, (size_t)(frag_base + n_new_frags + 1), st));
+        CMPT_HIP(grow_keep(c->name_bytes, Keep{(size_t)bytes_old}, (size_t)(bytes_old + bytes_new), st));
+        CMPT_HIP(grow_keep(c->name_off, Keep{(size_t)n_old + 1}, (size_t)(n_old + n_new + 1), st));
+        CMPT_HIP(grow_keep(c->frag_start, Keep{(size_t)frag_base + 1}, (size_t)(frag_base + n_new_frags + 1), st));
         CMPT_HIP(hipEventRecord(c->ev[7], st));
         hipLaunchKernelGGL(k_cmpt_assign, dim3(gv), dim3(BLOCK), 0, st, L, n_valid, (const uint32_t*)c->where.p, (const uint32_t*)c->is_new.p,
                            (const uint32_t*)c->rank.p, (const u64*)c->byte_off.p, n_old, bytes_old, n_new, bytes_new, c->slot.p, c->name_bytes.p, c->name_off.p);
@@ -577,7 +534,7 @@ int print_rows(cmpt_ctx* c, const cmp_row* rows, int64_t n_rows, cmpt_print_resu
     CMPT_HIP(hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(k_cmpt_lengths, dim3(gl), dim3(BLOCK), 0, st, rows, n_out, D, c->out_len.p, c->bad_row.p);
     hipcub::TransformInputIterator<u64, Widen, const uint32_t*> lengths(c->out_len.p, Widen());     // 32-bit lengths, a 64-bit sum
-    CMPT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, lengths, c->out_dst.p, (int)(n_out + 1), st); }));
+    CMPT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, lengths, c->out_dst.p, (int)(n_out + 1), st); }));
     CMPT_HIP(hipEventRecord(c->ev[1], st));
     u64 bad = 0, total = 0;
     CMPT_HIP(hipMemcpyAsync(&bad, c->bad_row.p, sizeof(u64), hipMemcpyDeviceToHost, st));

@@ -90,6 +90,28 @@ struct DeviceBuffer {
     }
 };
 
+// The leading elements grow_keep carries over: a type of its own, so that a call cannot swap it with the size it asks for.
+struct Keep {
+    size_t n;
+};
+
+// Room for `need` elements without losing the first keep.n, whatever the buffer's Size policy.  Growth is geometric, so the
+// bytes copied over a stream of pieces stay linear in its size.  The stream is synchronised before the old memory is freed.
+template <typename T, class Size>
+hipError_t grow_keep(DeviceBuffer<T, Size>& b, Keep keep, size_t need, hipStream_t st)
+{
+    if (b.p && need <= b.cap) return hipSuccess;
+    const size_t want = std::max(Size::of(need), 2 * b.cap);
+    DeviceBuffer<T, Size> next;
+    hipError_t e = hipMalloc((void**)&next.p, want * sizeof(T));
+    if (e != hipSuccess) return e;
+    next.cap = want;
+    if (keep.n && b.p) e = hipMemcpyAsync(next.p, b.p, keep.n * sizeof(T), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) b.swap(next);
+    return e;
+}
+
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;

@@ -3,7 +3,7 @@
 // store's last record (rec_tail / rec_commit), so that rec_sort and rec_text can bring the sorted file down.
 //
 // A piece (rect_add), n_lines lines:
-//   tables  the newline and tab positions of txt_shared.hpp (k_txt_count, k_txt_totals, k_txt_tables), tabs included;
+//   tables  the newline and tab positions of txt_shared.hpp, tabs included;
 //   parse   k_rect_lines: lane i takes line i, finds its fields in the tab table, applies rect_shared.hpp's rule and writes the
 //           40-byte record at tail index i.  Every line in front of the stop gives exactly one record, so the record index is
 //           the line index and nothing is compacted; records written behind the stop are not committed.  The stop is an
@@ -39,7 +39,6 @@ thread_local std::string g_rect_err;
 #define RECT_HIP(call) HIPHOST_TRY(g_rect_err, call)
 #define RECT_FAIL(code, ...) hiphost::fail(g_rect_err, code, __VA_ARGS__)
 
-constexpr size_t TEXT_PAD = CHUNK;            // zeroed: the last chunk is whole
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 static_assert(sizeof(dsa_record) == 40 && sizeof(rect_result) == 64 && sizeof(rect_timing) == 32, "C ABI layout");
@@ -55,24 +54,11 @@ struct RectOut {
     u64 others_before;          // the same over the lines in front of the stop (counted only if there is one)
 };
 
-struct TabAt {
-    const uint32_t* tab_pos;    // the line's first tab
-    __device__ int64_t operator()(int64_t k) const { return (int64_t)tab_pos[k]; }
-};
-
-struct DeviceInt {
-    __device__ bool operator()(const uint8_t* p, int64_t n, int& v) const { return field_int(p, n, v); }
-};
-
-// line i < n_lines of the text.  A line's tabs are tab_pos[t0 .. t1): t0 and t1 come from the table beside the newlines and
-// are used only if they lie inside the tab table.
+// line i < n_lines of the text
 __device__ inline rect_line parse_at(const Lines& L, int64_t i)
 {
-    const int64_t s = line_start(L, i), e = line_end(L, i);
-    const int64_t t0 = i == 0 ? 0 : (int64_t)L.nl_tab[i - 1];
-    const int64_t t1 = i < L.n_nl ? (int64_t)L.nl_tab[i] : L.n_tab;
-    const bool inside = t0 >= 0 && t0 <= t1 && t1 <= L.n_tab;
-    return rect_parse_line(L.text, s, e, inside ? t1 - t0 : 0, TabAt{L.tab_pos + (inside ? t0 : 0)}, DeviceInt());
+    const LineAt a = line_at(L, i);
+    return rect_parse_line(L.text, a.s, a.e, a.n_tabs, TabAt{L.tab_pos + a.t0}, DeviceInt());
 }
 
 // A record is ten ints at a multiple of 40 bytes from an allocation's start: 8-byte aligned (rec_load of rec_api.hip).
@@ -146,63 +132,33 @@ struct rect_ctx {
     hiphost::Stream st;
     hiphost::Event ev[3];
     rect_timing timing{};
-    DeviceBuffer<uint8_t, GrowSize> text, tmp;
-    DeviceBuffer<u64, GrowSize> blk, blk_off;
-    DeviceBuffer<Totals> totals;
-    DeviceBuffer<uint32_t, GrowSize> nl_pos, nl_tab, tab_pos;
+    DeviceBuffer<uint8_t, GrowSize> text;
+    TextScratch scratch;
+    TextTables tables;
     DeviceBuffer<RectOut> out;
 };
 
 namespace {
-
-// with final = 0 nothing behind the last newline is a line: it is not sent up
-int64_t whole_lines(const uint8_t* text, int64_t len)
-{
-    const void* nl = len ? memrchr(text, '\n', (size_t)len) : nullptr;
-    return nl ? (int64_t)((const uint8_t*)nl - text) + 1 : 0;
-}
 
 // `len` > 0
 int add_run(rect_ctx* c, rec_store* store, const uint8_t* text, int64_t len, int32_t final, rect_result* result)
 {
     RECT_HIP(hipSetDevice(c->device));
     hipStream_t st = c->st;
-    const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
-    const int64_t n_blocks = (n_chunks + BLOCK - 1) / BLOCK;
-    RECT_HIP(c->text.reserve((size_t)(n_chunks * CHUNK) + TEXT_PAD));
-    RECT_HIP(c->blk.reserve((size_t)n_blocks));
-    RECT_HIP(c->blk_off.reserve((size_t)n_blocks));
-    RECT_HIP(c->totals.reserve(1));
+    RECT_HIP(c->text.reserve(padded_size(len)));
     RECT_HIP(c->out.reserve(1));
-    RECT_HIP(hipEventRecord(c->ev[0], st));
-    RECT_HIP(hipMemcpyAsync(c->text.p, text, (size_t)len, hipMemcpyHostToDevice, st));
-    RECT_HIP(hipMemsetAsync(c->text.p + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
-    RECT_HIP(hipEventRecord(c->ev[1], st));
-    const uint4* chunks = reinterpret_cast<const uint4*>(c->text.p);
-    hipLaunchKernelGGL(k_txt_count<true>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, c->blk.p);
-    RECT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->blk.p, c->blk_off.p, (int)n_blocks, st); }));
-    hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(64), 0, st, (const u64*)c->blk.p, (const u64*)c->blk_off.p, n_blocks, (const uint8_t*)c->text.p, len,
-                       c->totals.p);
     Totals tot{};
-    RECT_HIP(hipMemcpyAsync(&tot, c->totals.p, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    RECT_HIP(hipStreamSynchronize(st));
-    RECT_HIP(hipGetLastError());
-    const int64_t n_nl = (int64_t)tot.n_nl, n_tab = (int64_t)tot.n_tab;
-    if (n_nl > len || n_tab > len) return RECT_FAIL(DSA_E_DEVICE, "internal: %lld newlines and %lld tabs in %lld bytes", (long long)n_nl, (long long)n_tab, (long long)len);
-    const int64_t n_lines = n_nl + ((final && tot.last != '\n') ? 1 : 0);      // at least one: the text is not empty
+    if (const int rc = text_upload_count<true>(g_rect_err, c->scratch, c->text.p, text, hipMemcpyHostToDevice, len, c->ev[0], c->ev[1], st, tot)) return rc;
+    const int64_t n_lines = (int64_t)tot.n_nl + ((final && tot.last != '\n') ? 1 : 0);      // at least one: the text is not empty
     // room behind the store's last record, one record per line; the store's bound is checked here, before anything is written
     void* tail = nullptr;
     if (const int rc = rec_tail(store, n_lines, &tail)) return RECT_FAIL(rc, "rect_add: %s", rec_last_error());
     RECT_HIP(hipSetDevice(c->device));
-    RECT_HIP(c->nl_pos.reserve((size_t)n_nl));
-    RECT_HIP(c->nl_tab.reserve((size_t)n_nl));
-    RECT_HIP(c->tab_pos.reserve((size_t)n_tab));
-    hipLaunchKernelGGL(k_txt_tables<true>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, (const u64*)c->blk_off.p, n_nl, n_tab, c->nl_pos.p,
-                       c->nl_tab.p, c->tab_pos.p);
+    RECT_HIP(c->tables.reserve(tot));
+    const Lines L = c->tables.place<true>(c->scratch, c->text.p, len, tot, st);
     RectOut out{};
     out.stop = out.other = NONE;
     RECT_HIP(hipMemcpyAsync(c->out.p, &out, sizeof(RectOut), hipMemcpyHostToDevice, st));
-    const Lines L{c->text.p, c->nl_pos.p, c->nl_tab.p, c->tab_pos.p, len, n_nl, n_tab};
     hipLaunchKernelGGL(k_rect_lines<true>, dim3(grid_of(n_lines)), dim3(BLOCK), 0, st, L, n_lines, static_cast<dsa_record*>(tail), c->out.p);
     uint32_t stop = NONE;
     RECT_HIP(hipMemcpyAsync(&stop, &c->out.p->stop, sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -47,12 +47,11 @@ thread_local std::string g_sct_err;
 #define SCT_HIP(call) HIPHOST_TRY(g_sct_err, call)
 #define SCT_FAIL(code, ...) hiphost::fail(g_sct_err, code, __VA_ARGS__)
 
-constexpr size_t TEXT_PAD = 2 * CHUNK;        // zeroed: the last chunk is whole, and the gather's look-ahead (SRC_PAD) fits
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int RUN_LINES = 64;                 // a run of kept lines is cut at every multiple of this inside its piece
 constexpr int RUN_GROUP = 16;                 // lanes per run in the gather (measured against 64: profiles/sctext/README.md)
 constexpr uint8_t END0 = 8;                   // meta: the kind in bits 0-2, "clusterEnd == 0" in bit 3
-static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");
+static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");        // k_sct_gather reads the pieces' texts
 
 struct PieceView {
     const uint8_t* text;
@@ -221,10 +220,6 @@ __global__ __launch_bounds__(BLOCK) void k_sct_heads(const PieceView* __restrict
     head[g] = h;
 }
 
-struct Widen {
-    __host__ __device__ u64 operator()(uint32_t v) const { return (u64)v; }
-};
-
 // one thread, after the two exclusive sums
 __global__ void k_sct_totals(int64_t n_lines, const uint32_t* __restrict__ klen, const u64* __restrict__ dst, const uint32_t* __restrict__ head,
                              const uint32_t* __restrict__ rank, Summary* __restrict__ sum)
@@ -260,8 +255,7 @@ __global__ __launch_bounds__(BLOCK) void k_sct_runs(const PieceView* __restrict_
 }
 
 // k_bat_gather of bat_shared.hpp without the reverse complement and with the source chosen per run: a group of G lanes owns a
-// run, lane i forms the aligned output dword i (+ G, + 2G ...) from two aligned source dwords; dword stores go only to dwords
-// wholly inside the run, the up to three bytes before the first and after the last of them out as byte stores.
+// run and copies it by copy_span.
 template <int G>
 __global__ __launch_bounds__(BLOCK) void k_sct_gather(const Run* __restrict__ run, int64_t n_runs, const PieceView* __restrict__ pv, int n_pieces,
                                                       uint8_t* __restrict__ dst, int64_t dst_len)
@@ -275,20 +269,9 @@ __global__ __launch_bounds__(BLOCK) void k_sct_gather(const Run* __restrict__ ru
     const uint8_t* __restrict__ src = pv[r.piece].text;
     const int64_t src_len = pv[r.piece].len;
     const int64_t len = (int64_t)r.len;
-    const int64_t d0 = r.dst, d1 = d0 + len;
-    if (len == 0 || d0 < 0 || d1 > dst_len || r.src < 0 || r.src + len > src_len) return;
-    const uint32_t* __restrict__ srcw = reinterpret_cast<const uint32_t*>(src);
-    uint32_t* __restrict__ dstw = reinterpret_cast<uint32_t*>(dst);
-    const int64_t w0 = (d0 + 3) & ~(int64_t)3, w1 = d1 & ~(int64_t)3;
-    for (int64_t p = w0 + 4 * lane; p < w1; p += 4 * G) dstw[p >> 2] = load_word(srcw, r.src + (p - d0));
-    const int64_t h1 = w0 < d1 ? w0 : d1;
-    const int64_t t0 = w1 > h1 ? w1 : h1;
-    const int64_t nh = h1 - d0, nt = d1 - t0;
-    const int64_t b = G - 1 - lane;
-    if (b < nh + nt) {
-        const int64_t p = b < nh ? d0 + b : t0 + (b - nh);
-        dst[p] = src[r.src + (p - d0)];
-    }
+    const int64_t d0 = r.dst;
+    if (len == 0 || d0 < 0 || d0 + len > dst_len || r.src < 0 || r.src + len > src_len) return;
+    (void)copy_span<G>(src, r.src, dst, d0, len, lane);
 }
 
 struct Piece {
@@ -306,10 +289,7 @@ struct sct_ctx {
     sct_timing timing{};
     std::vector<std::unique_ptr<Piece>> pieces;
     int64_t n_lines = 0, n_bytes = 0;
-    // scratch of a piece's tables
-    DeviceBuffer<u64, GrowSize> blk, blk_off;
-    DeviceBuffer<Totals> totals;
-    DeviceBuffer<uint8_t, GrowSize> tmp;
+    TextScratch scratch;        // of a piece's tables
     // per line, over all pieces
     DeviceBuffer<PieceView, GrowSize> views;
     DeviceBuffer<int32_t, GrowSize> cid, frag;
@@ -326,45 +306,20 @@ struct sct_ctx {
 
 namespace {
 
-// with final = 0 nothing behind the last newline is a line: it is not sent up
-int64_t whole_lines(const uint8_t* text, int64_t len)
-{
-    const void* nl = len ? memrchr(text, '\n', (size_t)len) : nullptr;
-    return nl ? (int64_t)((const uint8_t*)nl - text) + 1 : 0;
-}
-
 // One piece into device memory (padded with zeros) with its newline table.  `len` > 0.
 int add_piece(sct_ctx* c, const uint8_t* text, int64_t len)
 {
     SCT_HIP(hipSetDevice(c->device));
     hipStream_t st = c->st;
-    const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
-    const int64_t n_blocks = (n_chunks + BLOCK - 1) / BLOCK;
     std::unique_ptr<Piece> pc(new Piece());
-    SCT_HIP(pc->text.reserve((size_t)(n_chunks * CHUNK) + TEXT_PAD));
-    SCT_HIP(c->blk.reserve((size_t)n_blocks));
-    SCT_HIP(c->blk_off.reserve((size_t)n_blocks));
-    SCT_HIP(c->totals.reserve(1));
-    SCT_HIP(hipEventRecord(c->ev[0], st));
-    SCT_HIP(hipMemcpyAsync(pc->text.p, text, (size_t)len, hipMemcpyHostToDevice, st));
-    SCT_HIP(hipMemsetAsync(pc->text.p + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
-    SCT_HIP(hipEventRecord(c->ev[1], st));
-    const uint4* chunks = reinterpret_cast<const uint4*>(pc->text.p);
-    hipLaunchKernelGGL(k_txt_count<false>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, c->blk.p);
-    SCT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->blk.p, c->blk_off.p, (int)n_blocks, st); }));
-    hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(64), 0, st, (const u64*)c->blk.p, (const u64*)c->blk_off.p, n_blocks, (const uint8_t*)pc->text.p, len,
-                       c->totals.p);
+    SCT_HIP(pc->text.reserve(padded_size(len)));
     Totals tot{};
-    SCT_HIP(hipMemcpyAsync(&tot, c->totals.p, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    SCT_HIP(hipStreamSynchronize(st));
-    SCT_HIP(hipGetLastError());
+    if (const int rc = text_upload_count<false>(g_sct_err, c->scratch, pc->text.p, text, hipMemcpyHostToDevice, len, c->ev[0], c->ev[1], st, tot)) return rc;
     const int64_t n_nl = (int64_t)tot.n_nl;
-    if (n_nl > len) return SCT_FAIL(DSA_E_DEVICE, "internal: %lld newlines in %lld bytes", (long long)n_nl, (long long)len);
     const int64_t n_lines = n_nl + (tot.last != '\n' ? 1 : 0);
     if (c->n_lines + n_lines > (int64_t)INT32_MAX) return SCT_FAIL(DSA_E_LIMIT, "more than 2^31 - 1 cluster lines");
     SCT_HIP(pc->nl_pos.reserve((size_t)n_nl));
-    hipLaunchKernelGGL(k_txt_tables<false>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, (const u64*)c->blk_off.p, n_nl, (int64_t)0,
-                       pc->nl_pos.p, (uint32_t*)nullptr, (uint32_t*)nullptr);
+    text_place_tables<false>(c->scratch, pc->text.p, len, tot, pc->nl_pos.p, nullptr, nullptr, st);
     SCT_HIP(hipEventRecord(c->ev[2], st));
     SCT_HIP(hipStreamSynchronize(st));
     SCT_HIP(hipGetLastError());
@@ -470,10 +425,10 @@ int cover_run(sct_ctx* c, int64_t min_size, sct_result* r)
         SCT_HIP(d_coff.reserve((size_t)n_clusters + 1));
         hipcub::TransformInputIterator<u64, PackMember, hipcub::CountingInputIterator<int64_t>> pairs(hipcub::CountingInputIterator<int64_t>(0),
                                                                                                       PackMember{c->cid.p, c->frag.p});
-        SCT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        SCT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceSelect::Flagged(w, wb, pairs, c->keep.p, m_pair.p, d_count.p, (int)n, st);
         }));
-        SCT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {         // stable, by the cluster half only: file order inside a cluster
+        SCT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {         // stable, by the cluster half only: file order inside a cluster
             return hipcub::DeviceRadixSort::SortKeys(w, wb, m_pair.p, s_pair.p, (int)n_members, 32, 32 + bits_for(sum.max_cid), st);
         }));
         hipLaunchKernelGGL(k_sct_unpack, dim3(grid_of(n_members)), dim3(BLOCK), 0, st, (const u64*)s_pair.p, n_members, s_cid.p, d_el.p);
@@ -507,8 +462,8 @@ int cover_run(sct_ctx* c, int64_t min_size, sct_result* r)
                        (const int32_t*)c->owner.p, (const int32_t*)d_size.p, n_clusters, max_element, min_size, c->keep.p, c->klen.p, c->summary.p);
     hipLaunchKernelGGL(k_sct_heads, dim3(gl), dim3(BLOCK), 0, st, pv, np, n, (const uint8_t*)c->keep.p, c->head.p);
     hipcub::TransformInputIterator<u64, Widen, const uint32_t*> lengths(c->klen.p, Widen());      // 32-bit lengths, a 64-bit sum
-    SCT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, lengths, c->dst.p, (int)n, st); }));
-    SCT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->head.p, c->rank.p, (int)n, st); }));
+    SCT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, lengths, c->dst.p, (int)n, st); }));
+    SCT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->head.p, c->rank.p, (int)n, st); }));
     hipLaunchKernelGGL(k_sct_totals, dim3(1), dim3(64), 0, st, n, (const uint32_t*)c->klen.p, (const u64*)c->dst.p, (const uint32_t*)c->head.p,
                        (const uint32_t*)c->rank.p, c->summary.p);
     SCT_HIP(hipEventRecord(c->ev[4], st));

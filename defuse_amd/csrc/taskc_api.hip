@@ -47,22 +47,19 @@ namespace {
 using hiphost::DeviceBuffer;
 using hiphost::GrowSize;
 using hiphost::grid_of;
+using hiphost::grow_keep;
+using hiphost::Keep;
 
 thread_local std::string g_taskc_err;
 
 #define TASKC_HIP(call) HIPHOST_TRY(g_taskc_err, call)
 #define TASKC_FAIL(code, ...) hiphost::fail(g_taskc_err, code, __VA_ARGS__)
 
-constexpr size_t TEXT_PAD = 2 * CHUNK;        // zeroed behind the last piece: whole chunks, and the gather's look-ahead
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t SIGN = 0x80000000u;        // int order as unsigned order
 constexpr int LINE_GROUP = 16;                // lanes per copied line and per printed region
-static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");
+static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");        // k_gather reads the text; the padding lies behind the last piece
 static_assert(sizeof(taskc_result) == 96 && sizeof(taskc_timing) == 48 && sizeof(taskc_line) == 44, "layout");
-
-struct DeviceInt {
-    __device__ bool operator()(const uint8_t* p, int64_t n, int& v) const { return field_int(p, n, v); }
-};
 
 // what the host reads between the stages (in: the stops NONE, the counts 0)
 struct Summary {
@@ -271,9 +268,8 @@ __global__ __launch_bounds__(BLOCK) void k_out_lines(const uint32_t* __restrict_
     odst[k + 1] = fdst[j] + (u64)llen[a] + 1ull;
 }
 
-// k_bat_gather's scheme with a line per group of G lanes: lane i forms the aligned output dword i (+ G, + 2G ...) from two
-// aligned source dwords; dword stores go only to dwords wholly inside the line, the up to three bytes in front of the first and
-// behind the last of them out as byte stores; the lane that has no such byte stores the newline.
+// k_bat_gather's scheme with a line per group of G lanes, which copy it by copy_span; the first lane that has no head or tail
+// byte of the line stores the newline.
 template <int G>
 __global__ __launch_bounds__(BLOCK) void k_gather(const uint32_t* __restrict__ osrc, const u64* __restrict__ odst, int64_t n_out, const uint8_t* __restrict__ text,
                                                    int64_t text_len, const int64_t* __restrict__ lstart, const int32_t* __restrict__ llen, int64_t m,
@@ -288,18 +284,8 @@ __global__ __launch_bounds__(BLOCK) void k_gather(const uint32_t* __restrict__ o
     const int64_t src = lstart[i], len = llen[i];
     const int64_t d0 = (int64_t)odst[k], d1 = d0 + len;
     if (d0 < 0 || d1 + 1 > dst_len || src < 0 || src + len > text_len) return;
-    const uint32_t* __restrict__ srcw = reinterpret_cast<const uint32_t*>(text);
-    uint32_t* __restrict__ dstw = reinterpret_cast<uint32_t*>(dst);
-    const int64_t w0 = (d0 + 3) & ~(int64_t)3, w1 = d1 & ~(int64_t)3;
-    for (int64_t p = w0 + 4 * lane; p < w1; p += 4 * G) dstw[p >> 2] = load_word(srcw, src + (p - d0));
-    const int64_t h1 = w0 < d1 ? w0 : d1;
-    const int64_t t0 = w1 > h1 ? w1 : h1;
-    const int64_t nh = h1 - d0, nt = d1 - t0;                   // at most three each
-    const int64_t b = G - 1 - lane;
-    if (b < nh + nt) {
-        const int64_t p = b < nh ? d0 + b : t0 + (b - nh);
-        dst[p] = text[src + (p - d0)];
-    } else if (b == nh + nt) dst[d1] = '\n';
+    const int64_t n_edge = copy_span<G>(text, src, dst, d0, len, lane);       // at most six
+    if (G - 1 - lane == n_edge) dst[d1] = '\n';
 }
 
 // ---- regions ---------------------------------------------------------------------------------------------------------
@@ -410,19 +396,6 @@ struct Piece {                  // host: where a piece lies
     int64_t buf_base, in_base, len, line_base, n_lines;
 };
 
-// A buffer that grows and keeps its first `used` elements.
-template <typename T>
-hipError_t grow_keep(DeviceBuffer<T>& b, size_t need, size_t used, hipStream_t st)
-{
-    if (b.p && need <= b.cap) return hipSuccess;
-    DeviceBuffer<T> nb;
-    hipError_t e = nb.reserve(std::max(need + need / 8 + 64, 2 * b.cap));
-    if (e == hipSuccess && used) e = hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);           // the old memory is freed below
-    if (e == hipSuccess) b.swap(nb);
-    return e;
-}
-
 int bits_for(int64_t max_value)
 {
     int bits = 1;
@@ -444,10 +417,8 @@ struct taskc_ctx {
     std::vector<Piece> pieces;
     int64_t text_used = 0, n_lines = 0, n_bytes = 0;
     // scratch of a piece's tables
-    DeviceBuffer<u64, GrowSize> blk, blk_off;
-    DeviceBuffer<Totals> totals;
+    TextScratch scratch;
     DeviceBuffer<uint32_t, GrowSize> nl_pos;
-    DeviceBuffer<uint8_t, GrowSize> tmp;
     // the parsed lines
     DeviceBuffer<taskc_line, GrowSize> rec;
     DeviceBuffer<Summary> sum;
@@ -478,12 +449,6 @@ struct taskc_ctx {
 
 namespace {
 
-int64_t whole_lines(const uint8_t* text, int64_t len)
-{
-    const void* nl = len ? memrchr(text, '\n', (size_t)len) : nullptr;
-    return nl ? (int64_t)((const uint8_t*)nl - text) + 1 : 0;
-}
-
 void drop_outputs(taskc_ctx* c)
 {
     c->has_dedup = c->has_regions = c->parsed = false;
@@ -498,41 +463,24 @@ int add_piece(taskc_ctx* c, const uint8_t* src, int64_t len, hipMemcpyKind kind)
     TASKC_HIP(hipSetDevice(c->device));
     hipStream_t st = c->st;
     const int64_t base = c->text_used;
-    const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
-    const int64_t n_blocks = (n_chunks + BLOCK - 1) / BLOCK;
-    TASKC_HIP(grow_keep(c->text, (size_t)(base + n_chunks * CHUNK) + TEXT_PAD, (size_t)base, st));
-    TASKC_HIP(c->blk.reserve((size_t)n_blocks));
-    TASKC_HIP(c->blk_off.reserve((size_t)n_blocks));
-    TASKC_HIP(c->totals.reserve(1));
+    TASKC_HIP(grow_keep(c->text, Keep{(size_t)base}, (size_t)base + padded_size(len), st));
     uint8_t* at = c->text.p + base;
-    TASKC_HIP(hipEventRecord(c->ev[0], st));
-    TASKC_HIP(hipMemcpyAsync(at, src, (size_t)len, kind, st));
-    TASKC_HIP(hipMemsetAsync(at + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
-    TASKC_HIP(hipEventRecord(c->ev[1], st));
-    const uint4* chunks = reinterpret_cast<const uint4*>(at);
-    hipLaunchKernelGGL(k_txt_count<false>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, c->blk.p);
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->blk.p, c->blk_off.p, (int)n_blocks, st); }));
-    hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(64), 0, st, (const u64*)c->blk.p, (const u64*)c->blk_off.p, n_blocks, (const uint8_t*)at, len, c->totals.p);
     Totals tot{};
-    TASKC_HIP(hipMemcpyAsync(&tot, c->totals.p, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    TASKC_HIP(hipStreamSynchronize(st));
-    TASKC_HIP(hipGetLastError());
+    if (const int rc = text_upload_count<false>(g_taskc_err, c->scratch, at, src, kind, len, c->ev[0], c->ev[1], st, tot)) return rc;
     const int64_t n_nl = (int64_t)tot.n_nl;
-    if (n_nl > len) return TASKC_FAIL(DSA_E_DEVICE, "internal: %lld newlines in %lld bytes", (long long)n_nl, (long long)len);
     const int64_t n_lines = n_nl + (tot.last != '\n' ? 1 : 0);
     if (c->n_lines + n_lines > (int64_t)INT32_MAX) return TASKC_FAIL(DSA_E_LIMIT, "more than 2^31 - 1 cluster lines");
     TASKC_HIP(c->nl_pos.reserve((size_t)n_nl));
-    TASKC_HIP(grow_keep(c->lstart, (size_t)(c->n_lines + n_lines), (size_t)c->n_lines, st));
-    TASKC_HIP(grow_keep(c->llen, (size_t)(c->n_lines + n_lines), (size_t)c->n_lines, st));
-    hipLaunchKernelGGL(k_txt_tables<false>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, (const u64*)c->blk_off.p, n_nl, (int64_t)0, c->nl_pos.p,
-                       (uint32_t*)nullptr, (uint32_t*)nullptr);
+    TASKC_HIP(grow_keep(c->lstart, Keep{(size_t)c->n_lines}, (size_t)(c->n_lines + n_lines), st));
+    TASKC_HIP(grow_keep(c->llen, Keep{(size_t)c->n_lines}, (size_t)(c->n_lines + n_lines), st));
+    text_place_tables<false>(c->scratch, at, len, tot, c->nl_pos.p, nullptr, nullptr, st);
     hipLaunchKernelGGL(k_piece_lines, dim3(grid_of(n_lines)), dim3(BLOCK), 0, st, (const uint32_t*)c->nl_pos.p, n_nl, n_lines, base, len, c->lstart.p + c->n_lines,
                        c->llen.p + c->n_lines);
     TASKC_HIP(hipEventRecord(c->ev[2], st));
     TASKC_HIP(hipStreamSynchronize(st));
     TASKC_HIP(hipGetLastError());
     c->pieces.push_back(Piece{base, c->n_bytes, len, c->n_lines, n_lines});
-    c->text_used = base + n_chunks * CHUNK;
+    c->text_used = base + chunks_of(len) * CHUNK;
     c->n_lines += n_lines;
     c->n_bytes += len;
     c->timing.upload_ms += hiphost::elapsed(c->ev[0], c->ev[1]);
@@ -629,9 +577,9 @@ int dedup_run(taskc_ctx* c, int64_t min_size, taskc_result* r)
     for (auto* b : {&c->head, &c->runp, &c->k32[0], &c->k32[1], &c->idx[0], &c->idx[1]}) TASKC_HIP(b->reserve((size_t)m));
     TASKC_HIP(c->run_first.reserve((size_t)m + 1));
     hipLaunchKernelGGL(k_run_heads, dim3(grid_of(m)), dim3(BLOCK), 0, st, (const taskc_line*)c->rec.p, m, c->head.p, c->k32[0].p, c->idx[0].p, c->sum.p);
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->runp.p, (int)m, st); }));
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->runp.p, (int)m, st); }));
     hipLaunchKernelGGL(k_run_first, dim3(grid_of(m)), dim3(BLOCK), 0, st, (const uint32_t*)c->head.p, (const uint32_t*)c->runp.p, m, c->run_first.p, c->sum.p);
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
         return hipcub::DeviceRadixSort::SortPairs(w, wb, (const uint32_t*)c->k32[0].p, c->k32[1].p, (const uint32_t*)c->idx[0].p, c->idx[1].p, (int)m, 0, 2, st);
     }));
     if (const int rc = read_summary(c)) return rc;
@@ -646,12 +594,12 @@ int dedup_run(taskc_ctx* c, int64_t min_size, taskc_result* r)
         TASKC_HIP(c->win.reserve(2 * (size_t)F));
         hipLaunchKernelGGL(k_frag_keys, dim3(grid_of(F)), dim3(BLOCK), 0, st, (const uint32_t*)c->idx[1].p, (const taskc_line*)c->rec.p, (const uint32_t*)c->runp.p, F, m,
                            c->k64[0].p);
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceRadixSort::SortPairs(w, wb, (const u64*)c->k64[0].p, c->k64[1].p, (const uint32_t*)c->idx[1].p, c->idx[0].p, (int)F, 0,
                                                       32 + bits_for(n_runs - 1), st);
         }));
         hipLaunchKernelGGL(k_key_heads, dim3(grid_of(F)), dim3(BLOCK), 0, st, (const u64*)c->k64[1].p, F, c->hd.p);
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->hd.p, c->fp.p, (int)F, st); }));
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->hd.p, c->fp.p, (int)F, st); }));
         TASKC_HIP(hipMemsetAsync(c->win.p, 0xFF, 2 * (size_t)F * sizeof(uint32_t), st));
         hipLaunchKernelGGL(k_winners, dim3(grid_of(F)), dim3(BLOCK), 0, st, (const u64*)c->k64[1].p, (const uint32_t*)c->idx[0].p, (const taskc_line*)c->rec.p,
                            (const uint32_t*)c->fp.p, F, m, c->win.p, c->fkey.p, c->sum.p);
@@ -665,12 +613,12 @@ int dedup_run(taskc_ctx* c, int64_t min_size, taskc_result* r)
         hipLaunchKernelGGL(k_frag_pos, dim3(grid_of(nf)), dim3(BLOCK), 0, st, (const uint32_t*)c->win.p, (const u64*)c->fkey.p, (const taskc_line*)c->rec.p, nf, m,
                            open_tail ? (uint32_t)(n_runs - 1) : NONE, c->p0.p, c->p1.p, c->k32[0].p, c->idx[1].p, c->sum.p);
         // the order by (run, position 0, position 1), the lowest fragment first
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceRadixSort::SortPairs(w, wb, (const uint32_t*)c->k32[0].p, c->k32[1].p, (const uint32_t*)c->idx[1].p, c->idx[0].p, (int)nf, 0, 32, st);
         }));
         hipLaunchKernelGGL(k_pos_keys, dim3(grid_of(nf)), dim3(BLOCK), 0, st, (const uint32_t*)c->idx[0].p, (const u64*)c->fkey.p, (const int32_t*)c->p0.p, nf,
                            c->k64[0].p);
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceRadixSort::SortPairs(w, wb, (const u64*)c->k64[0].p, c->k64[1].p, (const uint32_t*)c->idx[0].p, c->idx[1].p, (int)nf, 0,
                                                       32 + bits_for(n_runs - 1), st);
         }));
@@ -702,7 +650,7 @@ int dedup_run(taskc_ctx* c, int64_t min_size, taskc_result* r)
         TASKC_HIP(c->odst.reserve(2 * (size_t)nf));
         hipLaunchKernelGGL(k_dup_heads, dim3(grid_of(nf)), dim3(BLOCK), 0, st, (const u64*)c->k64[1].p, (const uint32_t*)c->idx[1].p, (const int32_t*)c->p1.p, nf, c->hd.p,
                            c->keepf.p);
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->hd.p, c->hp.p, (int)nf, st); }));
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->hd.p, c->hp.p, (int)nf, st); }));
         hipLaunchKernelGGL(k_run_edges, dim3(grid_of(nf)), dim3(BLOCK), 0, st, (const u64*)c->k64[1].p, (const uint32_t*)c->hd.p, (const uint32_t*)c->hp.p, nf, n_runs,
                            c->rlo.p, c->rhi.p);
     }
@@ -710,8 +658,8 @@ int dedup_run(taskc_ctx* c, int64_t min_size, taskc_result* r)
     if (nf) {
         hipLaunchKernelGGL(k_frag_out, dim3(grid_of(nf)), dim3(BLOCK), 0, st, (const u64*)c->fkey.p, (const uint32_t*)c->keepf.p, (const uint32_t*)c->rlo.p,
                            (const uint32_t*)c->rhi.p, (const uint32_t*)c->win.p, (const int32_t*)c->llen.p, nf, n_runs, m, min_size, c->of.p, c->flen.p);
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->of.p, c->orank.p, (int)nf, st); }));
-        TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->flen.p, c->fdst.p, (int)nf, st); }));
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->of.p, c->orank.p, (int)nf, st); }));
+        TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->flen.p, c->fdst.p, (int)nf, st); }));
         hipLaunchKernelGGL(k_out_lines, dim3(grid_of(nf)), dim3(BLOCK), 0, st, (const uint32_t*)c->of.p, (const uint32_t*)c->orank.p, (const u64*)c->flen.p,
                            (const u64*)c->fdst.p, (const uint32_t*)c->win.p, (const int32_t*)c->llen.p, nf, c->osrc.p, c->odst.p, c->sum.p);
     }
@@ -783,24 +731,24 @@ int regions_run(taskc_ctx* c, bool from_dedup, taskc_result* r)
         return DSA_OK;
     }
     // the order by (id, end); groups; least start, greatest end, last line
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
         return hipcub::DeviceRadixSort::SortPairs(w, wb, (const u64*)c->k64[0].p, c->k64[1].p, (const uint32_t*)c->idx[0].p, c->idx[1].p, (int)q, 0, 64, st);
     }));
     hipLaunchKernelGGL(k_key_heads, dim3(grid_of(q)), dim3(BLOCK), 0, st, (const u64*)c->k64[1].p, q, c->head.p);
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->runp.p, (int)q, st); }));
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->runp.p, (int)q, st); }));
     hipLaunchKernelGGL(k_region_vals, dim3(grid_of(q)), dim3(BLOCK), 0, st, (const u64*)c->k64[1].p, (const uint32_t*)c->idx[1].p, (const uint32_t*)c->runp.p,
                        (const taskc_line*)c->rec.p, src, q, m, c->vstart.p, c->vend.p, c->glast.p, c->sum.p);
     u64* gkey = c->k64[0].p;                                    // (the unsorted keys are done with)
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
         return hipcub::DeviceReduce::ReduceByKey(w, wb, (const u64*)c->k64[1].p, gkey, (const int32_t*)c->vstart.p, c->gmin.p, c->n_unique.p, hipcub::Min(), (int)q, st);
     }));
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
         return hipcub::DeviceReduce::ReduceByKey(w, wb, (const u64*)c->k64[1].p, gkey, (const int32_t*)c->vend.p, c->gmax.p, c->n_unique.p, hipcub::Max(), (int)q, st);
     }));
     hipLaunchKernelGGL(k_region_groups, dim3(grid_of(q)), dim3(BLOCK), 0, st, (const u64*)gkey, (const int32_t*)c->gmin.p, (const int32_t*)c->gmax.p,
                        (const uint32_t*)c->glast.p, (const taskc_line*)c->rec.p, q, m, c->glen.p, c->sum.p);
     TASKC_HIP(hipEventRecord(c->ev[10], st));
-    TASKC_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->glen.p, c->gdst.p, (int)q, st); }));
+    TASKC_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->glen.p, c->gdst.p, (int)q, st); }));
     hipLaunchKernelGGL(k_region_total, dim3(1), dim3(64), 0, st, (const u64*)c->glen.p, (const u64*)c->gdst.p, q, c->sum.p);
     if (const int rc = read_summary(c)) return rc;
     const int64_t n_groups = sum.n_groups, out_bytes = sum.out_bytes;

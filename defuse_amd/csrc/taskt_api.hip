@@ -62,36 +62,12 @@ thread_local std::string g_taskt_err;
 #define TASKT_HIP(call) HIPHOST_TRY(g_taskt_err, call)
 #define TASKT_FAIL(code, ...) hiphost::fail(g_taskt_err, code, __VA_ARGS__)
 
-constexpr size_t TEXT_PAD = CHUNK;            // zeroed: the last chunk is whole
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr u64 NO_END = 1ull << 33;            // the sort key of a line that gives no end: behind every (id, end)
 constexpr int KEY_BITS = 34;
 
 static_assert(sizeof(taskt_result) == 80 && sizeof(taskt_timing) == 40 && sizeof(taskt_region_line) == 40, "layout");
 static_assert(TASKT_MAX_NAME % 8 == 0, "whole chunks");
-
-struct TabAt {
-    const uint32_t* tab_pos;    // the line's first tab
-    __device__ int64_t operator()(int64_t k) const { return (int64_t)tab_pos[k]; }
-};
-
-struct DeviceInt {
-    __device__ bool operator()(const uint8_t* p, int64_t n, int& v) const { return field_int(p, n, v); }
-};
-
-// Line i < n_lines: its bytes [s, e) and its tabs tab_pos[t0 .. t0 + n_tabs); t0 and n_tabs come from the table beside the
-// newlines and are used only if they lie inside the tab table.
-struct LineAt {
-    int64_t s, e, t0, n_tabs;
-};
-
-__device__ inline LineAt line_at(const Lines& L, int64_t i)
-{
-    const int64_t t0 = i == 0 ? 0 : (int64_t)L.nl_tab[i - 1];
-    const int64_t t1 = i < L.n_nl ? (int64_t)L.nl_tab[i] : L.n_tab;
-    const bool inside = t0 >= 0 && t0 <= t1 && t1 <= L.n_tab;
-    return LineAt{line_start(L, i), line_end(L, i), inside ? t0 : 0, inside ? t1 - t0 : 0};
-}
 
 // ---- exon table -----------------------------------------------------------------------------------------------------
 
@@ -438,11 +414,9 @@ struct taskt_ctx {
     hiphost::Event ev[8];       // 0-2 exons: start, text up, kernels done; 3-5 regions likewise; 6, 7 around the pairs' checks
     taskt_timing timing{};
     // the text tables and the scratch of either parse
-    DeviceBuffer<u64, GrowSize> blk, blk_off;
-    DeviceBuffer<uint32_t, GrowSize> nl_pos, nl_tab, tab_pos;
-    DeviceBuffer<Totals> totals;
+    TextScratch scratch;
+    TextTables tables;
     DeviceBuffer<ParseOut> out;
-    DeviceBuffer<uint8_t, GrowSize> tmp;
     DeviceBuffer<u64, GrowSize> cnt, cnt_off, key[2];
     DeviceBuffer<uint32_t, GrowSize> idx[2], head, grp, first, rank;
     Lines L{};
@@ -495,34 +469,13 @@ int load_text(taskt_ctx* c, DeviceBuffer<uint8_t, GrowSize>& text, const uint8_t
               hipMemcpyKind kind = hipMemcpyHostToDevice)
 {
     hipStream_t st = c->st;
-    const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
-    const int64_t n_blocks = (n_chunks + BLOCK - 1) / BLOCK;
-    TASKT_HIP(text.reserve((size_t)(n_chunks * CHUNK) + TEXT_PAD));
-    TASKT_HIP(c->blk.reserve((size_t)n_blocks));
-    TASKT_HIP(c->blk_off.reserve((size_t)n_blocks));
-    TASKT_HIP(c->totals.reserve(1));
+    TASKT_HIP(text.reserve(padded_size(len)));
     TASKT_HIP(c->out.reserve(1));
-    TASKT_HIP(hipEventRecord(start, st));
-    TASKT_HIP(hipMemcpyAsync(text.p, host, (size_t)len, kind, st));
-    TASKT_HIP(hipMemsetAsync(text.p + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
-    TASKT_HIP(hipEventRecord(up, st));
-    const uint4* chunks = reinterpret_cast<const uint4*>(text.p);
-    hipLaunchKernelGGL(k_txt_count<true>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, c->blk.p);
-    TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->blk.p, c->blk_off.p, (int)n_blocks, st); }));
-    hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(64), 0, st, (const u64*)c->blk.p, (const u64*)c->blk_off.p, n_blocks, (const uint8_t*)text.p, len, c->totals.p);
     Totals& tot = c->h_tot;
-    TASKT_HIP(hipMemcpyAsync(&tot, c->totals.p, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    TASKT_HIP(hipStreamSynchronize(st));
-    TASKT_HIP(hipGetLastError());
-    const int64_t n_nl = (int64_t)tot.n_nl, n_tab = (int64_t)tot.n_tab;
-    if (n_nl > len || n_tab > len) return TASKT_FAIL(DSA_E_DEVICE, "internal: %lld newlines and %lld tabs in %lld bytes", (long long)n_nl, (long long)n_tab, (long long)len);
-    TASKT_HIP(c->nl_pos.reserve((size_t)n_nl));
-    TASKT_HIP(c->nl_tab.reserve((size_t)n_nl));
-    TASKT_HIP(c->tab_pos.reserve((size_t)n_tab));
-    hipLaunchKernelGGL(k_txt_tables<true>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, (const u64*)c->blk_off.p, n_nl, n_tab, c->nl_pos.p,
-                       c->nl_tab.p, c->tab_pos.p);
-    c->L = Lines{text.p, c->nl_pos.p, c->nl_tab.p, c->tab_pos.p, len, n_nl, n_tab};
-    c->n_lines = n_nl + (tot.last != '\n' ? 1 : 0);         // at least one: the text is not empty
+    if (const int rc = text_upload_count<true>(g_taskt_err, c->scratch, text.p, host, kind, len, start, up, st, tot)) return rc;
+    TASKT_HIP(c->tables.reserve(tot));
+    c->L = c->tables.place<true>(c->scratch, text.p, len, tot, st);
+    c->n_lines = (int64_t)tot.n_nl + (tot.last != '\n' ? 1 : 0);         // at least one: the text is not empty
     c->h_out = ParseOut{};
     c->h_out.stop = c->h_out.dup = NONE;
     TASKT_HIP(hipMemcpyAsync(c->out.p, &c->h_out, sizeof(ParseOut), hipMemcpyHostToDevice, st));
@@ -561,7 +514,7 @@ int sort_names(taskt_ctx* c, const uint8_t* text, const int64_t* off, const int3
     for (int pass = -1; pass < chunks; ++pass) {
         const int chunk = pass < 0 ? -1 : chunks - 1 - pass;
         hipLaunchKernelGGL(k_name_keys, dim3(grid_of(n)), dim3(BLOCK), 0, st, text, off, len, (const uint32_t*)c->idx[cur].p, n, chunk, c->key[0].p);
-        TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        TASKT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceRadixSort::SortPairs(w, wb, (const u64*)c->key[0].p, c->key[1].p, (const uint32_t*)c->idx[cur].p, c->idx[1 - cur].p, (int)n, 0,
                                                       chunk < 0 ? 8 : 64, st);
         }));
@@ -580,7 +533,7 @@ int parse_exons(taskt_ctx* c, const taskt_names* ref, const uint8_t* text, int64
     TASKT_HIP(c->cnt.reserve((size_t)n_lines));
     TASKT_HIP(c->cnt_off.reserve((size_t)n_lines));
     hipLaunchKernelGGL(k_exon_lines, dim3(grid_of(n_lines)), dim3(BLOCK), 0, st, L, n_lines, c->cnt.p, c->out.p);
-    TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->cnt.p, c->cnt_off.p, (int)n_lines, st); }));
+    TASKT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->cnt.p, c->cnt_off.p, (int)n_lines, st); }));
     hipLaunchKernelGGL(k_exon_total, dim3(1), dim3(64), 0, st, (const u64*)c->cnt.p, (const u64*)c->cnt_off.p, n_lines, c->out.p);
     ParseOut& out = c->h_out;
     TASKT_HIP(hipMemcpyAsync(&out, c->out.p, sizeof(ParseOut), hipMemcpyDeviceToHost, st));
@@ -640,10 +593,10 @@ int parse_exons(taskt_ctx* c, const taskt_names* ref, const uint8_t* text, int64
         if (const int rc = sort_names(c, L.text, c->cn_off.p, c->cn_len.p, n_rows, max_len, &order)) return rc;
         hipLaunchKernelGGL(k_name_heads, dim3(grid_of(n_rows)), dim3(BLOCK), 0, st, L.text, (const int64_t*)c->cn_off.p, (const int32_t*)c->cn_len.p, order, n_rows,
                            c->head.p);
-        TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->grp.p, (int)n_rows, st); }));
+        TASKT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->grp.p, (int)n_rows, st); }));
         TASKT_HIP(hipMemsetAsync(c->first.p, 0, (size_t)n_rows * sizeof(uint32_t), st));
         hipLaunchKernelGGL(k_chrom_first, dim3(grid_of(n_rows)), dim3(BLOCK), 0, st, (const uint32_t*)c->head.p, order, n_rows, c->first.p);
-        TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->first.p, c->rank.p, (int)n_rows, st); }));
+        TASKT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->first.p, c->rank.p, (int)n_rows, st); }));
         hipLaunchKernelGGL(k_chrom_groups, dim3(grid_of(n_rows)), dim3(BLOCK), 0, st, L.text, (const uint32_t*)c->head.p, (const uint32_t*)c->grp.p, order,
                            (const uint32_t*)c->rank.p, (const int64_t*)c->cn_off.p, (const int32_t*)c->cn_len.p, n_rows, ref->view(), c->grp_off.p, c->grp_len.p,
                            c->grp_cid.p, c->chrom_ref.p);
@@ -718,13 +671,13 @@ int parse_regions(taskt_ctx* c, const taskt_names* seqs, const uint8_t* text, in
         TASKT_HIP(c->rank.reserve((size_t)n_valid));
         TASKT_HIP(c->pairs.reserve((size_t)n_valid));
         TASKT_HIP(c->plines.reserve(2 * (size_t)n_valid));
-        TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+        TASKT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
             return hipcub::DeviceRadixSort::SortPairs(w, wb, (const u64*)c->key[0].p, c->key[1].p, (const uint32_t*)c->idx[0].p, c->idx[1].p, (int)n_lines, 0, KEY_BITS,
                                                       st);
         }));
         const Resolver R = resolver(c, seqs);
         hipLaunchKernelGGL(k_id_heads, dim3(grid_of(n_valid)), dim3(BLOCK), 0, st, (const u64*)c->key[1].p, n_valid, c->head.p);
-        TASKT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->rank.p, (int)n_valid, st); }));
+        TASKT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::InclusiveSum(w, wb, c->head.p, c->rank.p, (int)n_valid, st); }));
         hipLaunchKernelGGL(k_pairs_fill, dim3(grid_of(n_valid)), dim3(BLOCK), 0, st, (const u64*)c->key[1].p, (const uint32_t*)c->head.p, (const uint32_t*)c->rank.p,
                            n_valid, R, L.text, c->pairs.p, c->plines.p, c->out.p);
         hipLaunchKernelGGL(k_pairs_win, dim3(grid_of(n_valid)), dim3(BLOCK), 0, st, (const u64*)c->key[1].p, (const uint32_t*)c->idx[1].p, (const uint32_t*)c->rank.p,

@@ -2,8 +2,7 @@
 // cand_alignment[] (ParseSamLine, tools_src/defuse_host.hpp) and the FASTQ text a read store of bytes + bat_read[]
 // (FastqReader::next + AddReads), both in device memory.
 //
-// Tables (both formats): the newline and tab positions of txt_shared.hpp (k_txt_count, k_txt_totals, k_txt_tables), which the
-//   set cover's cluster text (sct_api.hip) builds the same way.
+// Tables (both formats): the newline and tab positions of txt_shared.hpp, built by its host path like every other text's.
 // SAM: one lane per line reads its tab positions 1-4 and 9-10 from the table and only qname, flag, rname and pos from the
 //   text; the name is a binary search over the sorted names.  The first stop is an atomic minimum over the (rare) bad lines,
 //   the carried read end an inclusive scan with "the last value told", the records are compacted by an exclusive sum of
@@ -33,6 +32,7 @@ namespace {
 using hiphost::DeviceBuffer;
 using hiphost::GrowSize;
 using hiphost::grid_of;
+using hiphost::Keep;
 using batdev::Seg64;
 
 thread_local std::string g_txt_err;
@@ -40,11 +40,10 @@ thread_local std::string g_txt_err;
 #define TXT_HIP(call) HIPHOST_TRY(g_txt_err, call)
 #define TXT_FAIL(code, ...) hiphost::fail(g_txt_err, code, __VA_ARGS__)
 
-constexpr size_t TEXT_PAD = 2 * CHUNK;        // zeroed: the last chunk is whole, and the gather's look-ahead (SRC_PAD) fits
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int READ_GROUP = 16;                // lanes per sequence in the gather, as bat_api.hip
 constexpr uint8_t UNTOLD = 2;
-static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");
+static_assert(TEXT_PAD >= batdev::SRC_PAD + CHUNK, "padding");        // k_bat_gather reads the text
 
 // ---- SAM --------------------------------------------------------------------------------------------------------------
 
@@ -57,8 +56,7 @@ __global__ __launch_bounds__(BLOCK) void k_sam_lines(Lines L, int64_t n_lines, N
     if (i >= n_lines) return;
     const uint8_t* __restrict__ text = L.text;
     const int64_t s = line_start(L, i), e = line_end(L, i);
-    const int64_t t0 = i == 0 ? 0 : (int64_t)L.nl_tab[i - 1];
-    const int64_t t1 = i < L.n_nl ? (int64_t)L.nl_tab[i] : L.n_tab;
+    const int64_t t0 = first_tab_rank(L, i), t1 = end_tab_rank(L, i);
     int kind = 0;
     uint8_t re = UNTOLD;
     cand_alignment a{-1, 0, 0, 0, -1, 0};
@@ -234,10 +232,8 @@ struct txt_ctx {
     int32_t max_read_len = TXT_MAX_READ_LEN;
     // the text and its tables
     DeviceBuffer<uint8_t, GrowSize> text;
-    DeviceBuffer<u64, GrowSize> blk, blk_off;
-    DeviceBuffer<uint32_t, GrowSize> nl_pos, nl_tab, tab_pos;
-    DeviceBuffer<Totals> totals;
-    DeviceBuffer<uint8_t, GrowSize> tmp;
+    TextScratch scratch;
+    TextTables tables;
     Totals tot{};
     // SAM
     DeviceBuffer<cand_alignment, GrowSize> al_line, al;
@@ -261,65 +257,18 @@ struct txt_ctx {
 
 namespace {
 
-// room for `need` elements without losing the first `used`
-template <typename T>
-int grow_keep(DeviceBuffer<T, GrowSize>& b, size_t used, size_t need, hipStream_t st)
-{
-    if (b.p && need <= b.cap) return DSA_OK;
-    DeviceBuffer<T, GrowSize> next;
-    TXT_HIP(next.reserve(std::max(need, 2 * b.cap)));
-    if (used && b.p) {
-        TXT_HIP(hipMemcpyAsync(next.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st));
-        TXT_HIP(hipStreamSynchronize(st));
-    }
-    b.swap(next);
-    return DSA_OK;
-}
-
 // The text into the ctx (padded with zeros) and its tables.  `len` > 0.  On return c->tot holds the totals and the tables
-// are written; the stream has been synchronised once (for the totals).
+// are being written; the stream has been synchronised once (for the totals).
 template <bool TABS>
-int build_tables(txt_ctx* c, const void* text, int64_t len, bool on_device)
+int build_tables(txt_ctx* c, const void* text, int64_t len, bool on_device, Lines* L)
 {
-    hipStream_t st = c->st;
-    const int64_t n_chunks = (len + CHUNK - 1) / CHUNK;
-    const int64_t n_blocks = (n_chunks + BLOCK - 1) / BLOCK;
-    TXT_HIP(c->text.reserve((size_t)(n_chunks * CHUNK) + TEXT_PAD));
-    TXT_HIP(c->blk.reserve((size_t)n_blocks));
-    TXT_HIP(c->blk_off.reserve((size_t)n_blocks));
-    TXT_HIP(c->totals.reserve(1));
-    TXT_HIP(hipEventRecord(c->ev[0], st));
-    TXT_HIP(hipMemcpyAsync(c->text.p, text, (size_t)len, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    TXT_HIP(hipMemsetAsync(c->text.p + len, 0, (size_t)(n_chunks * CHUNK - len) + TEXT_PAD, st));
-    TXT_HIP(hipEventRecord(c->ev[1], st));
-    const uint4* chunks = reinterpret_cast<const uint4*>(c->text.p);
-    hipLaunchKernelGGL(k_txt_count<TABS>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, c->blk.p);
-    TXT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->blk.p, c->blk_off.p, (int)n_blocks, st); }));
-    hipLaunchKernelGGL(k_txt_totals, dim3(1), dim3(64), 0, st, (const u64*)c->blk.p, (const u64*)c->blk_off.p, n_blocks, (const uint8_t*)c->text.p, len,
-                       c->totals.p);
-    TXT_HIP(hipMemcpyAsync(&c->tot, c->totals.p, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    TXT_HIP(hipStreamSynchronize(st));
-    TXT_HIP(hipGetLastError());
-    const int64_t n_nl = (int64_t)c->tot.n_nl, n_tab = (int64_t)c->tot.n_tab;
-    if (n_nl > len || n_tab > len) return TXT_FAIL(DSA_E_DEVICE, "internal: %lld newlines and %lld tabs in %lld bytes", (long long)n_nl, (long long)n_tab, (long long)len);
-    TXT_HIP(c->nl_pos.reserve((size_t)n_nl));
-    TXT_HIP(c->nl_tab.reserve((size_t)n_nl));
-    TXT_HIP(c->tab_pos.reserve((size_t)n_tab));
-    hipLaunchKernelGGL(k_txt_tables<TABS>, dim3((unsigned)n_blocks), dim3(BLOCK), 0, st, chunks, n_chunks, (const u64*)c->blk_off.p, n_nl, n_tab, c->nl_pos.p,
-                       c->nl_tab.p, c->tab_pos.p);
+    TXT_HIP(c->text.reserve(padded_size(len)));
+    if (const int rc = text_upload_count<TABS>(g_txt_err, c->scratch, c->text.p, text, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, len, c->ev[0],
+                                               c->ev[1], c->st, c->tot))
+        return rc;
+    TXT_HIP(c->tables.reserve(c->tot));
+    *L = c->tables.place<TABS>(c->scratch, c->text.p, len, c->tot, c->st);
     return DSA_OK;
-}
-
-Lines lines_of(const txt_ctx* c, int64_t len)
-{
-    return Lines{c->text.p, c->nl_pos.p, c->nl_tab.p, c->tab_pos.p, len, (int64_t)c->tot.n_nl, (int64_t)c->tot.n_tab};
-}
-
-// with final = 0 nothing behind the last newline is a line: the host entry does not send it up
-int64_t whole_lines(const uint8_t* text, int64_t len)
-{
-    const void* nl = len ? memrchr(text, '\n', (size_t)len) : nullptr;
-    return nl ? (int64_t)((const uint8_t*)nl - text) + 1 : 0;
 }
 
 int parse_sam_run(txt_ctx* c, const txt_names* names, const void* text, int64_t len, int32_t final, int32_t carry_in, txt_sam_result* result, bool on_device);
@@ -351,7 +300,8 @@ int parse_sam_run(txt_ctx* c, const txt_names* names, const void* text, int64_t 
     if (!on_device && !final) len = whole_lines(static_cast<const uint8_t*>(text), len);
     if (len == 0) return DSA_OK;
     hipStream_t st = c->st;
-    if (const int rc = build_tables<true>(c, text, len, on_device)) return rc;
+    Lines L{};
+    if (const int rc = build_tables<true>(c, text, len, on_device, &L)) return rc;
     const int64_t n_lines = (int64_t)c->tot.n_nl + ((final && c->tot.last != '\n') ? 1 : 0);
     c->timing.text_bytes = len;
     if (n_lines == 0) {                             // (a device text without a newline and final = 0)
@@ -369,13 +319,12 @@ int parse_sam_run(txt_ctx* c, const txt_names* names, const void* text, int64_t 
     SamOut out{};
     out.stop = NONE;
     TXT_HIP(hipMemcpyAsync(c->sam_out.p, &out, sizeof(SamOut), hipMemcpyHostToDevice, st));
-    const Lines L = lines_of(c, len);
     const unsigned gl = grid_of(n_lines);
     hipLaunchKernelGGL(k_sam_lines, dim3(gl), dim3(BLOCK), 0, st, L, n_lines, names->view(), c->al_line.p, c->told.p, c->flag.p, &c->sam_out.p->stop);
-    TXT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) {
+    TXT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) {
         return hipcub::DeviceScan::InclusiveScan(w, wb, c->told.p, c->told_scan.p, LastTold(), (int)n_lines, st);
     }));
-    TXT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->flag.p, c->pos.p, (int)n_lines, st); }));
+    TXT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->flag.p, c->pos.p, (int)n_lines, st); }));
     hipLaunchKernelGGL(k_sam_emit, dim3(gl), dim3(BLOCK), 0, st, (const cand_alignment*)c->al_line.p, (const uint8_t*)c->told_scan.p, (const uint32_t*)c->flag.p,
                        (const uint32_t*)c->pos.p, n_lines, carry_in, c->al.p, c->line_of.p, c->sam_out.p);
     hipLaunchKernelGGL(k_sam_result, dim3(1), dim3(64), 0, st, L, n_lines, (const cand_alignment*)c->al_line.p, (const uint8_t*)c->told_scan.p,
@@ -530,7 +479,8 @@ int txt_fastq_add(txt_ctx* c, const uint8_t* text, int64_t len, int32_t final, t
     auto run = [&]() -> int {
         TXT_HIP(hipSetDevice(c->device));
         hipStream_t st = c->st;
-        if (const int rc = build_tables<false>(c, text, len, false)) return rc;
+        Lines L{};
+        if (const int rc = build_tables<false>(c, text, len, false, &L)) return rc;
         c->timing.text_bytes = len;
         const int64_t n_lines = (int64_t)c->tot.n_nl + ((final && c->tot.last != '\n') ? 1 : 0);
         const int64_t n_rec = n_lines / 4;
@@ -548,11 +498,10 @@ int txt_fastq_add(txt_ctx* c, const uint8_t* text, int64_t len, int32_t final, t
         FqOut out{};
         out.stop = NONE;
         TXT_HIP(hipMemcpyAsync(c->fq_out.p, &out, sizeof(FqOut), hipMemcpyHostToDevice, st));
-        const Lines L = lines_of(c, len);
         const unsigned gr = grid_of(n_rec);
         hipLaunchKernelGGL(k_fq_records, dim3(gr), dim3(BLOCK), 0, st, L, n_rec, c->max_read_len, c->fq_rec.p, c->cnt.p, c->slen.p, &c->fq_out.p->stop);
-        TXT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->cnt.p, c->cpos.p, (int)n_rec, st); }));
-        TXT_HIP(hiphost::cub_run(c->tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->slen.p, c->soff.p, (int)n_rec, st); }));
+        TXT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->cnt.p, c->cpos.p, (int)n_rec, st); }));
+        TXT_HIP(hiphost::cub_run(c->scratch.tmp, [&](void* w, size_t& wb) { return hipcub::DeviceScan::ExclusiveSum(w, wb, c->slen.p, c->soff.p, (int)n_rec, st); }));
         hipLaunchKernelGGL(k_fq_result, dim3(1), dim3(64), 0, st, L, n_rec, (const FqRec*)c->fq_rec.p, (const u64*)c->cnt.p, (const u64*)c->cpos.p,
                            (const u64*)c->slen.p, (const u64*)c->soff.p, c->fq_out.p);
         TXT_HIP(hipMemcpyAsync(&out, c->fq_out.p, sizeof(FqOut), hipMemcpyDeviceToHost, st));
@@ -561,8 +510,8 @@ int txt_fastq_add(txt_ctx* c, const uint8_t* text, int64_t len, int32_t final, t
         if (out.n_groups < 0 || out.n_groups > n_rec || out.n_records < 0 || out.n_records + out.n_skipped > out.n_groups || out.n_bytes < 0 || out.n_bytes > len)
             return TXT_FAIL(DSA_E_DEVICE, "internal: %lld records of %lld groups, %lld bytes", (long long)out.n_records, (long long)out.n_groups, (long long)out.n_bytes);
         if (out.n_records) {
-            if (const int rc = grow_keep(c->store_reads, (size_t)c->store_n, (size_t)(c->store_n + out.n_records), st)) return rc;
-            if (const int rc = grow_keep(c->store_bytes, (size_t)c->store_bytes_len, (size_t)(c->store_bytes_len + out.n_bytes) + 4, st)) return rc;      // whole dwords
+            TXT_HIP(hiphost::grow_keep(c->store_reads, Keep{(size_t)c->store_n}, (size_t)(c->store_n + out.n_records), st));
+            TXT_HIP(hiphost::grow_keep(c->store_bytes, Keep{(size_t)c->store_bytes_len}, (size_t)(c->store_bytes_len + out.n_bytes) + 4, st));            // whole dwords
             TXT_HIP(c->seg.reserve((size_t)out.n_records));
             hipLaunchKernelGGL(k_fq_emit, dim3(grid_of(out.n_groups)), dim3(BLOCK), 0, st, (const FqRec*)c->fq_rec.p, (const u64*)c->cpos.p, (const u64*)c->soff.p,
                                out.n_groups, out.n_records, c->store_n, c->store_bytes_len, c->store_reads.p, c->seg.p);
