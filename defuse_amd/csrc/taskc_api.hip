@@ -932,3 +932,18 @@ int taskc_get_timing(const taskc_ctx* c, taskc_timing* out)
 }
 
 }  // extern "C"
+
+// For span_api.hip: the parsed lines of the input (from_dedup false) or of the dedup text, where they lie.  Parses the input if
+// no step has yet; the ctx's stream is idle on return.  DSA_E_ARG (its text in taskc_last_error()) without a dedup text.
+__attribute__((visibility("hidden"))) int taskc_lines_device(taskc_ctx* c, bool from_dedup, taskc_lines_view* out)
+{
+    if (from_dedup && !c->has_dedup) return TASKC_FAIL(DSA_E_ARG, "the ctx has no dedup text (taskc_dedup first)");
+    TASKC_HIP(hipSetDevice(c->device));
+    if (const int rc = ensure_parsed(c)) {
+        (void)hipStreamSynchronize(c->st);
+        return rc;
+    }
+    *out = taskc_lines_view{c->device, c->text.p, c->lstart.p, c->llen.p, c->rec.p, from_dedup ? c->osrc.p : nullptr, c->n_lines,
+                            from_dedup ? c->dout_lines : c->n_lines};
+    return DSA_OK;
+}

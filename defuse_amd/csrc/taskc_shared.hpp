@@ -80,6 +80,19 @@ TASKC_HD taskc_line taskc_parse_line(const uint8_t* text, int64_t s, int64_t e, 
     return L;
 }
 
+// What a later step on the same device reads of a taskc_ctx in place (taskc_api.hip: taskc_lines_device; span_api.hip): the
+// text, every input line's start and length, its parsed record, and the lines of the source - item k of the source is input
+// line src[k], or k itself where src is null.  Device pointers, valid until the next call on the taskc_ctx.
+struct taskc_lines_view {
+    int device;
+    const uint8_t* text;
+    const int64_t* lstart;
+    const int32_t* llen;
+    const taskc_line* rec;
+    const uint32_t* src;
+    int64_t n_input_lines, n_lines;
+};
+
 // bytes of v in plain decimal
 TASKC_HD int taskc_dec_len(int32_t v)
 {

@@ -35,6 +35,9 @@
  * be told from the arguments alone are found before a device is touched.  One object must not be used from two threads at
  * once.  Out of scope: the tools (they keep their host formatters), the NaN and infinity texts of EVAL_HOST_STATS groups,
  * more than one GPU per chain, a streamed entry, locales other than C.
+ *
+ * A second section, "span statistics" (span_*), follows at the end: splitreads.span.stats from the same prediction and the
+ * cluster text of a taskc_ctx.
  */
 #ifndef DEFUSE_PTEXT_H_
 #define DEFUSE_PTEXT_H_
@@ -43,6 +46,7 @@
 
 #include "defuse_dsa.h"
 #include "defuse_pred.h"
+#include "defuse_task.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -128,6 +132,140 @@ int ptext_get_timing(const ptext_ctx* ctx, ptext_timing* out);
 int ptext_format_doubles(int device, const double* x, int64_t n, uint8_t* out, int64_t cap, int32_t* len, int64_t* out_len);
 
 const char* ptext_last_error(void);
+
+/* ---- span statistics ----------------------------------------------------------------------------------------------------
+ *
+ * splitreads.span.stats, the file scripts/calc_span_stats.pl makes right after evalsplitalign from clusters.sc,
+ * splitreads.break and splitreads.seq: per cluster the mean length of its spanning fragments up to the predicted break,
+ * and their number.  In a chain run both inputs are in device memory already: the de-duplicated cluster text in a taskc_ctx
+ * (defuse_task.h, "cluster text"), the break positions in a pred_ctx.
+ *
+ * Three maps, in each the last line of a key wins:
+ *     .break lines    break[(id, end)] = field 4        (fields 0, 1)
+ *     .seq lines      inter[id] = field 2               (field 0; WriteSequence prints 0 there)
+ *     cluster lines   strand[(id, end)] = field 5 of the last line of that (id, end), whatever its fragment;
+ *                     pos[(id, fragment, end)] = fields 6 and 7 of the last line of that triple (the winner)
+ * Rows, for every id of the cluster text that has any break entry (the others are skipped, whatever they are made of):
+ *     - the id has exactly two distinct cluster ends among its lines;
+ *     - every distinct fragment's length is the sum of one term per end THE FRAGMENT HAS, break - start + 1 if
+ *       strand[(id, end)] is exactly "+", else end - break + 1 (only the one position field the strand selects is read),
+ *       plus inter[id], once per fragment;
+ *     - sum = the sum over the fragments (an int64), count = their number, mean = (double)sum / (double)count;
+ *     - the text line "%d\t%.15g\t%lld\n" of id, mean, count: what Perl prints for the quotient while |sum| <= 2^53.
+ * Ids, ends and fragments are ints as in the cluster text section: "+7", "007" and "7" are one value, an id prints in plain
+ * decimal, groups are over the whole text, rows ascend by id (the script: hash order).  n_noncanonical counts the key fields
+ * (cluster fields 0, 1, 2; .break fields 0, 1; .seq field 0) that are not byte for byte the "%d" of their value: where it
+ * is 0, Perl's string keys and these int keys are the same keys.
+ *
+ * Stops end a call with DSA_OK and a filled result, and the ctx then holds no output of that call's kind.
+ *   Line stops, the lowest line of the file in question (.break before .seq in span_breaks_text): fewer than 8 / 5 / 3 fields
+ *   in a cluster / .break / .seq line is SPAN_FEW_FIELDS; cluster fields 0, 1, 2, .break fields 0, 1, 4 and .seq fields 0, 2
+ *   are integers (optional sign, digits, int range; "1e2", " 349" and "12\r" are none), else SPAN_BAD_INTEGER with the first
+ *   such field.  stop_line is 1-based in the text looked at (for TASKC_DEDUP the dedup text), stop_file says which.
+ *   Id stops, only for ids with a break entry, the lowest id as int, stop_line 0, stop_value the id; within one id the first of
+ *     SPAN_NOT_TWO_ENDS   not exactly two distinct cluster ends;
+ *     SPAN_NO_BREAK_END   a winner's (id, end) has no break entry;
+ *     SPAN_BAD_INTEGER    the position field a winner uses is no integer (stop_field 6 or 7, the lower if both occur);
+ *     SPAN_COORD_LIMIT    a break a winner uses, a position a winner uses, or the id's inter is beyond +-TASK_MAX_COORD,
+ *                         which keeps every sum inside an int64;
+ *     SPAN_NO_INTER       the id has no inter entry;
+ *     SPAN_SUM_LIMIT      |sum| > 2^53.
+ *   A line stop beats an id stop.
+ */
+#define SPAN_FEW_FIELDS     1
+#define SPAN_BAD_INTEGER    2
+#define SPAN_NOT_TWO_ENDS   3
+#define SPAN_NO_BREAK_END   4
+#define SPAN_COORD_LIMIT    5
+#define SPAN_NO_INTER       6
+#define SPAN_SUM_LIMIT      7
+#define SPAN_FILE_CLUSTERS  0      /* stop_file                                                                       */
+#define SPAN_FILE_BREAKS    1
+#define SPAN_FILE_SEQS      2
+
+typedef struct span_result {
+    int64_t n_lines;                   /* span_stats: cluster lines; span_breaks_text: .break lines; _pred: groups     */
+    int64_t n_seq_lines;               /* span_breaks_text: .seq lines                                                 */
+    int64_t n_breaks;                  /* span_breaks_*: distinct (id, end) of the break table                         */
+    int64_t n_inters;                  /* span_breaks_*: distinct ids of the inter table                               */
+    int64_t n_ids;                     /* span_stats: distinct ids of the cluster text                                 */
+    int64_t n_rows;                    /* span_stats: ids with a break entry                                           */
+    int64_t out_bytes;                 /* span_stats: bytes of the text                                                */
+    int64_t n_noncanonical;            /* key fields of this call's texts that are not their "%d"                      */
+    int64_t stop_line;                 /* 1-based; 0: no stop, or an id stop                                           */
+    int64_t stop_value;                /* an id stop: the id                                                           */
+    int32_t stop_kind;                 /* SPAN_*, 0: no stop                                                           */
+    int32_t stop_field;                /* SPAN_BAD_INTEGER: the field, else -1                                         */
+    int32_t stop_file;                 /* SPAN_FILE_*; meaningful with a stop                                          */
+    int32_t pad_;
+} span_result;
+
+typedef struct span_row {
+    int32_t cluster_id;
+    int32_t text_len;                  /* the row's line is text[text_off .. text_off + text_len)                      */
+    int64_t text_off;
+    int64_t count;                     /* distinct fragments                                                           */
+    int64_t sum;
+    double  mean;
+} span_row;
+
+/* The output of the latest span_stats of a ctx on the device; valid until the next call on the ctx or its destruction. */
+typedef struct span_device_view {
+    const void* rows;                  /* span_row[n_rows], ascending cluster_id; device pointers, never NULL          */
+    const void* text;
+    int64_t n_rows;
+    int64_t text_len;
+    int32_t device;
+    int32_t pad_;
+} span_device_view;
+
+/* HIP-event times of the most recent span_breaks_*, span_stats and span_fetch of a ctx. */
+typedef struct span_timing {
+    float   upload_ms;                 /* span_breaks_text: both texts to the device                                   */
+    float   lines_ms;                  /* span_breaks_*: line and tab tables and the line rules, or the pass over pred */
+    float   tables_ms;                 /* span_breaks_*: the two sorts, the last of each run                           */
+    float   sorts_ms;                  /* span_stats: keys, the two sorts, groups and strands                          */
+    float   terms_ms;                  /* span_stats: winners, lookups, terms, the sums, the rows' rules               */
+    float   print_ms;                  /* span_stats: offsets, rows and text                                           */
+    float   download_ms;               /* span_fetch                                                                   */
+    float   pad_;
+    int64_t n_lines;                   /* cluster lines of the latest span_stats                                       */
+    int64_t n_rows;
+} span_timing;
+
+typedef struct span_ctx span_ctx;      /* opaque: the two tables and the output of one caller, reused call after call  */
+
+int span_create(int device, span_ctx** out);
+void span_destroy(span_ctx* ctx);
+
+/* The two files as text, each whole (a last line without a newline is a line).  DSA_E_ARG for a negative length or a null
+ * pointer with a length, DSA_E_LIMIT for more than 2^31 - 1 bytes in either.  Leaves the sorted (id, end) -> break table and
+ * the id -> inter table on the device, replacing the ones before; after a stop or a failure the ctx has no tables. */
+int span_breaks_text(span_ctx* ctx, const uint8_t* brk_text, int64_t brk_len, const uint8_t* seq_text, int64_t seq_len, span_result* result);
+/* The same tables from the latest successful prediction of `pred`, read in place: for every group that gets .break lines
+ * (neither PRED_NO_TASK nor PRED_OUT_OF_WINDOW) two break entries with the position its .break lines carry (0 for a group
+ * without a split) and inter 0, PTEXT_HOST_SEQ groups included, whose .seq line carries the same 0.  DSA_E_ARG if an object
+ * is missing, the two are not on one device, or `pred` has no completed prediction. */
+int span_breaks_pred(span_ctx* ctx, const pred_ctx* pred, span_result* result);
+/* Rows and text over the cluster text of `clusters`: source TASKC_INPUT (the text as added) or TASKC_DEDUP (the output of
+ * its last taskc_dedup); the line records taskc parsed are reused.  DSA_E_ARG for another source, a missing object, objects
+ * on two devices, a ctx without tables, or TASKC_DEDUP without a dedup text. */
+int span_stats(span_ctx* ctx, taskc_ctx* clusters, int32_t source, span_result* result);
+
+/* DSA_E_ARG if the ctx has no output (no span_stats yet, or its latest one stopped or failed). */
+int span_view(const span_ctx* ctx, span_device_view* out);
+/* Downloads rows and text (a buffer whose capacity is 0 may be NULL; capacities in elements).  DSA_E_CAPACITY if either does
+ * not fit; nothing is written then. */
+int span_fetch(span_ctx* ctx, span_row* rows, int64_t rows_cap, uint8_t* text, int64_t text_cap);
+int span_get_timing(const span_ctx* ctx, span_timing* out);
+
+/* The "%.15g" texts of x[0 .. n) as the device build of the formatter prints them, back to back in out[0 .. *out_len);
+ * len[k] is the length of the k-th text, 0 where the formatter declines (it takes +-0 and 2^-64 <= |x| < 2^64).  *out_len
+ * receives the total on success and on DSA_E_CAPACITY (total > cap; out and len are not written then).  DSA_E_LIMIT:
+ * n > 2^30 - 1. */
+int span_format_doubles(int device, const double* x, int64_t n, uint8_t* out, int64_t cap, int32_t* len, int64_t* out_len);
+
+const char* span_last_error(void);
 
 #ifdef __cplusplus
 }

@@ -8,18 +8,22 @@
 //   defuse_glue divide_sam_chr_pairs -t <trans> -p <prefix>   scripts/divide_sam_chr_pairs.pl:9-177 (stdin -> files + list on stdout)
 //   defuse_glue sort_alignments [-o out] f1 f2 ...  the `sort -n -k 1` / `sort -m -n -k 1` of scripts/defuse_run.pl:528,533
 //   defuse_glue cluster_regions <min_size> -c clusters_out -r regions_out [clusters]   remove_duplicates, then get_align_regions
+//   defuse_glue calc_span_stats -c clusters -b breaks -s seqs   scripts/calc_span_stats.pl:37-126   (stdout)
+//   defuse_glue span_stats -c clusters -b breaks -s seqs [-o out]   calc_span_stats on the GPU
 //
 // A symlink named after a script (merge_clusters.pl -> defuse_glue) selects the subcommand by its own name, so the
 // pipeline's `$scripts_directory/<script>.pl` can point at it unchanged.  The script steps are host text work (the files are a
 // few hundred MB and every step is one pass), they are here because these steps sit between clustermatepairs, setcover and
-// dosplitalign and were the slowest links once those ran on the GPU.  Two steps have a device part: sort_alignments, the sort
-// between dosplitalign and evalsplitalign on the record store of include/defuse_rec.h, and cluster_regions, which does
-// remove_duplicates and get_align_regions in one process on the cluster text section of include/defuse_task.h.
+// dosplitalign and were the slowest links once those ran on the GPU.  Three steps have a device part: sort_alignments, the sort
+// between dosplitalign and evalsplitalign on the record store of include/defuse_rec.h, cluster_regions, which does
+// remove_duplicates and get_align_regions in one process on the cluster text section of include/defuse_task.h, and span_stats,
+// which is calc_span_stats on that section and the span statistics section of include/defuse_ptext.h.
 // Where a script's output order follows Perl's hash order (randomised per process), the canonical order of
 // SURVEY 8(c) is used: ascending numeric ids, chromosome names in string order.
 #include <chrono>
 
 #include "../include/defuse_dsa.h"
+#include "../include/defuse_ptext.h"
 #include "../include/defuse_rec.h"
 #include "../include/defuse_task.h"
 #include "defuse_host.hpp"
@@ -552,6 +556,246 @@ int cluster_regions(int argc, char** argv)
     return 0;
 }
 
+// -c/--clusters, -b/--breaks, -s/--seqs (and -o/--output where `out` is given) of the two span statistics steps
+bool span_arguments(int argc, char** argv, std::string& clusters, std::string& breaks, std::string& seqs, std::string* out)
+{
+    for (int a = 0; a < argc; ++a) {
+        const std::string t = argv[a];
+        std::string* into = (t == "-c" || t == "--clusters") ? &clusters : (t == "-b" || t == "--breaks") ? &breaks : (t == "-s" || t == "--seqs") ? &seqs
+                            : (out && (t == "-o" || t == "--output")) ? out : nullptr;
+        if (!into || a + 1 >= argc) return false;
+        *into = argv[++a];
+    }
+    return !clusters.empty() && !breaks.empty() && !seqs.empty();
+}
+
+// scripts/calc_span_stats.pl by the rules of include/defuse_ptext.h, "span statistics": per cluster with a break entry the
+// mean length of its spanning fragments up to the break and their number, "%d\t%.15g\t%lld\n", clusters ascending (the script:
+// Perl hash order).  Of every (cluster, end) the strand of its last line, of every (cluster, fragment, end) the positions of its
+// last line, of every key of the two small files its last line.  Anything that stops prints nothing and is status 1.
+int calc_span_stats(int argc, char** argv)
+{
+    std::string clusters_name, breaks_name, seqs_name;
+    if (!span_arguments(argc, argv, clusters_name, breaks_name, seqs_name, nullptr)) {
+        std::cerr << "Usage: calc_span_stats -c clusters -b breaks -s seqs > span_stats\n";
+        return 1;
+    }
+    const long long max_coord = TASK_MAX_COORD;
+    auto each_line = [](const MappedText& text, const std::function<void(size_t, const char*, size_t)>& fn) {
+        size_t n = 0;
+        for (size_t pos = 0; pos < text.size(); ++n) {
+            const char* nl = (const char*)memchr(text.data() + pos, '\n', text.size() - pos);
+            const size_t end = nl ? (size_t)(nl - text.data()) : text.size();
+            fn(n + 1, text.data() + pos, end - pos);
+            pos = end + 1;
+        }
+    };
+    auto line_stop = [](const std::string& name, size_t line, const std::string& why) { die("Error: " + name + " line " + std::to_string(line) + ": " + why); };
+    auto integer = [&](const std::string& name, size_t line, const Fields& f, int k) {
+        int v = 0;
+        if (!field_int(f.p[k], f.len(k), v)) line_stop(name, line, "field " + std::to_string(k + 1) + " is not an integer");
+        return v;
+    };
+    MappedText breaks, seqs, clusters;
+    if (!breaks.try_load(breaks_name, false)) die("Error: Unable to find " + breaks_name);
+    if (!seqs.try_load(seqs_name, false)) die("Error: Unable to find " + seqs_name);
+    if (!clusters.try_load(clusters_name, false)) die("Error: Unable to find " + clusters_name);
+    std::map<std::pair<int, int>, int> break_pos;
+    std::unordered_map<int, int> inter;
+    Fields f;
+    each_line(breaks, [&](size_t n, const char* line, size_t len) {
+        split_fields(line, len, 6, f);
+        if (f.n < 5) line_stop(breaks_name, n, "fewer than five fields");
+        const int id = integer(breaks_name, n, f, 0), end = integer(breaks_name, n, f, 1);
+        break_pos[{id, end}] = integer(breaks_name, n, f, 4);
+    });
+    each_line(seqs, [&](size_t n, const char* line, size_t len) {
+        split_fields(line, len, 4, f);
+        if (f.n < 3) line_stop(seqs_name, n, "fewer than three fields");
+        const int id = integer(seqs_name, n, f, 0);
+        inter[id] = integer(seqs_name, n, f, 2);
+    });
+    struct Line { int id, frag, ce; const char* strand; const char* start; const char* end; uint32_t strand_len, start_len, end_len; };
+    std::vector<Line> lines;
+    std::unordered_map<uint64_t, uint32_t> end_last;        // (id, end) -> its last line
+    each_line(clusters, [&](size_t n, const char* line, size_t len) {
+        split_fields(line, len, 9, f);
+        if (f.n < 8) line_stop(clusters_name, n, "fewer than eight fields");
+        const int id = integer(clusters_name, n, f, 0), ce = integer(clusters_name, n, f, 1), frag = integer(clusters_name, n, f, 2);
+        end_last[((uint64_t)(uint32_t)id << 32) | (uint32_t)ce] = (uint32_t)lines.size();
+        lines.push_back(Line{id, frag, ce, f.p[5], f.p[6], f.p[7], (uint32_t)f.len(5), (uint32_t)f.len(6), (uint32_t)f.len(7)});
+    });
+    std::vector<uint32_t> order(lines.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = (uint32_t)k;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const Line &x = lines[a], &y = lines[b];
+        return x.id != y.id ? x.id < y.id : x.frag != y.frag ? x.frag < y.frag : x.ce < y.ce;
+    });
+    std::string out;
+    char buf[96];
+    for (size_t lo = 0; lo < order.size();) {
+        const int id = lines[order[lo]].id;
+        size_t hi = lo;
+        while (hi < order.size() && lines[order[hi]].id == id) ++hi;
+        const auto first = break_pos.lower_bound({id, INT_MIN});
+        if (first == break_pos.end() || first->first.first != id) {            // the script: next if not defined
+            lo = hi;
+            continue;
+        }
+        // what stops the cluster, the first of the header's list
+        int rank = 7, bad_field = 0;
+        auto stop = [&](int r, int field = 0) { if (r < rank || (r == rank && field < bad_field)) { rank = r; bad_field = field; } };
+        std::vector<int> ends;
+        for (size_t k = lo; k < hi; ++k) ends.push_back(lines[order[k]].ce);
+        std::sort(ends.begin(), ends.end());
+        if (std::unique(ends.begin(), ends.end()) - ends.begin() != 2) stop(1);
+        long long sum = 0, count = 0;
+        for (size_t k = lo; k < hi; ++k) {
+            const Line& l = lines[order[k]];
+            if (k == lo || lines[order[k - 1]].frag != l.frag) ++count;
+            if (k + 1 < hi && lines[order[k + 1]].frag == l.frag && lines[order[k + 1]].ce == l.ce) continue;      // not the last of its (fragment, end)
+            const Line& s = lines[end_last[((uint64_t)(uint32_t)id << 32) | (uint32_t)l.ce]];
+            const bool plus = s.strand_len == 1 && s.strand[0] == '+';
+            const auto b = break_pos.find({id, l.ce});
+            if (b == break_pos.end()) stop(2);
+            else if (b->second > max_coord || b->second < -max_coord) stop(4);
+            int pos = 0;
+            if (!field_int(plus ? l.start : l.end, plus ? l.start_len : l.end_len, pos)) stop(3, plus ? 7 : 8);
+            else if (pos > max_coord || pos < -max_coord) stop(4);
+            if (rank == 7) sum += plus ? (long long)b->second - pos + 1 : (long long)pos - b->second + 1;
+        }
+        const auto in = inter.find(id);
+        if (in == inter.end()) stop(5);
+        else if (in->second > max_coord || in->second < -max_coord) stop(4);
+        else sum += (long long)in->second * count;
+        if (rank == 7 && (sum > (1ll << 53) || sum < -(1ll << 53))) stop(6);
+        if (rank == 1) die("Error: Did not find 2 reference names for cluster " + std::to_string(id));
+        if (rank < 7) {
+            const std::string why = rank == 2   ? "a cluster end has no entry in " + breaks_name
+                                    : rank == 3 ? "field " + std::to_string(bad_field) + " of a line whose position is used is not an integer"
+                                    : rank == 4 ? "a break, a position or the inter length is beyond +-" + std::to_string(max_coord)
+                                    : rank == 5 ? "the cluster has no entry in " + seqs_name
+                                                : "the sum of the fragment lengths is beyond 2^53";
+            die("Error: " + clusters_name + " cluster " + std::to_string(id) + ": " + why);
+        }
+        const int n = snprintf(buf, sizeof buf, "%d\t%.15g\t%lld\n", id, (double)sum / (double)count, count);
+        out.append(buf, (size_t)n);
+        lo = hi;
+    }
+    if (!out.empty() && fwrite(out.data(), 1, out.size(), stdout) != out.size()) die("Error: failed writing the span statistics");
+    return 0;
+}
+
+// calc_span_stats on the GPU (include/defuse_ptext.h, "span statistics"): the cluster file goes up in pieces through the cluster
+// text section, the two small files whole, OUT (or stdout) is what `calc_span_stats` prints.  Anything the host step would die of,
+// and a text whose key fields are not all plain "%d" (Perl keys its hashes by their bytes), is declined with status 3 and OUT
+// not touched, so that a caller falls back (`defuse_glue span_stats ... -o OUT || defuse_glue calc_span_stats ... > OUT`).  A
+// library failure, no GPU included, is status 1 with nothing written.
+int span_stats_tool(int argc, char** argv)
+{
+    std::string clusters_name, breaks_name, seqs_name, out_name;
+    if (!span_arguments(argc, argv, clusters_name, breaks_name, seqs_name, &out_name)) {
+        std::cerr << "Usage: span_stats -c clusters -b breaks -s seqs [-o out]\n";
+        return 1;
+    }
+    const bool timing = std::getenv("DEFUSE_TIMING") != nullptr;
+    int64_t piece_bytes = (int64_t)1 << 30;
+    if (const char* pb = std::getenv("DEFUSE_GLUE_PIECE_BYTES")) {
+        char* end = nullptr;
+        const long long v = strtoll(pb, &end, 10);
+        if (end == pb || *end || v < 1) die(std::string("Error: DEFUSE_GLUE_PIECE_BYTES is not a positive number: ") + pb);
+        piece_bytes = std::min<long long>(v, INT32_MAX);
+    }
+    auto finish = [](int rc) {
+        std::cout.flush();
+        std::cerr.flush();
+        fflush(nullptr);
+        if (std::getenv("DEFUSE_FULL_EXIT")) exit(rc);      // under a profiler that writes its files at exit
+        _exit(rc);                                          // no teardown of a runtime whose work is done
+    };
+    auto lib_failed = [&](const char* what, const char* err) { std::cerr << "Error: span_stats on the GPU failed: " << what << ": " << err << std::endl; finish(1); };
+    const double t0 = now();
+    MappedText clusters, breaks, seqs;
+    if (!breaks.try_load(breaks_name, false)) die("Error: Unable to find " + breaks_name);
+    if (!seqs.try_load(seqs_name, false)) die("Error: Unable to find " + seqs_name);
+    if (!clusters.try_load(clusters_name, false, false)) die("Error: Unable to find " + clusters_name);
+    const double t_map = now();
+    const int device = dsa_pick_device();
+    taskc_ctx* text = nullptr;
+    span_ctx* ctx = nullptr;
+    if (taskc_create(device, &text) != 0) lib_failed("taskc_create", taskc_last_error());
+    if (span_create(device, &ctx) != 0) lib_failed("span_create", span_last_error());
+    if (taskc_begin(text) != 0) lib_failed("taskc_begin", taskc_last_error());
+    for (size_t pos = 0; pos < clusters.size();) {
+        size_t hi = std::min(clusters.size(), pos + (size_t)piece_bytes);
+        int64_t consumed = 0;
+        for (;;) {
+            if (taskc_add(text, (const uint8_t*)clusters.data() + pos, (int64_t)(hi - pos), hi == clusters.size() ? 1 : 0, &consumed) != 0)
+                lib_failed("taskc_add", taskc_last_error());
+            if (consumed > 0 || hi == clusters.size()) break;
+            hi = clusters.line_end(hi);                     // a line longer than a piece goes up whole
+        }
+        pos += (size_t)consumed;
+    }
+    const double t_up = now();
+    auto decline = [&](const span_result& r) {
+        std::cerr << "span_stats";
+        if (r.stop_kind) std::cerr << ": " << (r.stop_file == SPAN_FILE_BREAKS ? breaks_name : r.stop_file == SPAN_FILE_SEQS ? seqs_name : clusters_name);
+        if (r.stop_line) std::cerr << " line " << r.stop_line;
+        else if (r.stop_kind) std::cerr << " cluster " << r.stop_value;
+        if (r.stop_kind == SPAN_FEW_FIELDS) std::cerr << ": too few fields";
+        else if (r.stop_kind == SPAN_BAD_INTEGER) std::cerr << ": field " << r.stop_field + 1 << " is not an integer";
+        else if (r.stop_kind == SPAN_NOT_TWO_ENDS) std::cerr << ": not two cluster ends";
+        else if (r.stop_kind == SPAN_NO_BREAK_END) std::cerr << ": a cluster end without a break";
+        else if (r.stop_kind == SPAN_COORD_LIMIT) std::cerr << ": a coordinate beyond +-" << TASK_MAX_COORD;
+        else if (r.stop_kind == SPAN_NO_INTER) std::cerr << ": no inter length";
+        else if (r.stop_kind == SPAN_SUM_LIMIT) std::cerr << ": a sum beyond 2^53";
+        else std::cerr << ": " << r.n_noncanonical << " key field(s) not in plain decimal";
+        std::cerr << "; nothing written, use calc_span_stats" << std::endl;
+        finish(3);
+    };
+    span_result bres, sres;
+    if (span_breaks_text(ctx, (const uint8_t*)breaks.data(), (int64_t)breaks.size(), (const uint8_t*)seqs.data(), (int64_t)seqs.size(), &bres) != 0)
+        lib_failed("span_breaks_text", span_last_error());
+    if (bres.stop_kind) decline(bres);
+    if (span_stats(ctx, text, TASKC_INPUT, &sres) != 0) lib_failed("span_stats", span_last_error());
+    if (sres.stop_kind) decline(sres);
+    sres.n_noncanonical += bres.n_noncanonical;
+    if (sres.n_noncanonical) decline(sres);
+    const double t_dev = now();
+    std::unique_ptr<span_row[]> rows(new span_row[(size_t)sres.n_rows + 1]);
+    std::unique_ptr<uint8_t[]> bytes(new uint8_t[(size_t)sres.out_bytes + 1]);
+    if (span_fetch(ctx, rows.get(), sres.n_rows, bytes.get(), sres.out_bytes) != 0) lib_failed("span_fetch", span_last_error());
+    const double t_down = now();
+    if (out_name.empty()) {
+        if (sres.out_bytes && fwrite(bytes.get(), 1, (size_t)sres.out_bytes, stdout) != (size_t)sres.out_bytes) die("Error: failed writing the span statistics");
+    } else {
+        const int fd = open(out_name.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (fd < 0) die("Error: unable to write to " + out_name);
+        for (size_t done = 0; done < (size_t)sres.out_bytes;) {
+            const ssize_t w = write(fd, bytes.get() + done, (size_t)sres.out_bytes - done);
+            if (w <= 0) die("Error: failed writing " + out_name);
+            done += (size_t)w;
+        }
+        if (close(fd) != 0) die("Error: failed writing " + out_name);
+    }
+    const double t_write = now();
+    if (timing) {
+        span_timing t{};
+        taskc_timing tc{};
+        (void)span_get_timing(ctx, &t);
+        (void)taskc_get_timing(text, &tc);
+        std::cerr << "[span_stats] " << clusters.size() << " bytes, " << sres.n_lines << " lines in " << tc.n_pieces << " piece(s), " << bres.n_breaks << " breaks, "
+                  << sres.n_ids << " clusters, " << sres.n_rows << " rows: map " << t_map - t0 << " s, create+upload " << t_up - t_map << " s, tables+stats "
+                  << t_dev - t_up << " s, download " << t_down - t_dev << " s, write " << t_write - t_down << " s\n"
+                  << "[span_stats] device: upload " << tc.upload_ms << " ms, line tables " << tc.tables_ms << " ms, parse " << tc.parse_ms << " ms, breaks upload "
+                  << t.upload_ms << " ms, lines " << t.lines_ms << " ms, tables " << t.tables_ms << " ms, sorts " << t.sorts_ms << " ms, terms " << t.terms_ms
+                  << " ms, print " << t.print_ms << " ms, download " << t.download_ms << " ms" << std::endl;
+    }
+    finish(0);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[])
@@ -563,7 +807,8 @@ int main(int argc, char* argv[])
     int first = 1;
     if (prog == "defuse_glue") {
         if (argc < 2) {
-            std::cerr << "Usage: defuse_glue merge_clusters|get_align_regions|remove_duplicates|filter_unmatched|divide_sam_chr_pairs|sort_alignments|cluster_regions [args]\n";
+            std::cerr << "Usage: defuse_glue merge_clusters|get_align_regions|remove_duplicates|filter_unmatched|divide_sam_chr_pairs|calc_span_stats|sort_alignments|"
+                         "cluster_regions|span_stats [args]\n";
             return 1;
         }
         prog = argv[1];
@@ -577,6 +822,8 @@ int main(int argc, char* argv[])
         if (prog == "divide_sam_chr_pairs") return divide_sam_chr_pairs(argc - first, argv + first);
         if (prog == "sort_alignments") return sort_alignments(argc - first, argv + first);
         if (prog == "cluster_regions") return cluster_regions(argc - first, argv + first);
+        if (prog == "calc_span_stats") return calc_span_stats(argc - first, argv + first);
+        if (prog == "span_stats") return span_stats_tool(argc - first, argv + first);
     } catch (const GlueError& g) {
         die(g.msg);
     }
