@@ -22,7 +22,9 @@
 //
 // Two ways in: la_align_batch_min takes references and sequences from one host pool (k_pack fills the codes);
 // la_align_windows_min (matealign) cuts every reference out of a genome kept in HBM by la_genome_create, from a
-// 40-byte descriptor per pair (k_pack_win).  Both run the same launch groups and the same two kernels.
+// 40-byte descriptor per pair (k_pack_win).  A third, la_align_pairs_device (la_pairs.hpp, for conc_api.hip), takes both sides of a
+// pair from sequence bytes in HBM, each with its own reverse-complement flag (k_pack_pairs), and leaves the scores on the device.
+// All run the same launch groups and the same two kernels.
 #include <hip/hip_runtime.h>
 
 #include "hip_host.hpp"
@@ -38,6 +40,7 @@
 
 #include "../../include/defuse_dsa.h"
 #include "../../include/defuse_la.h"
+#include "la_pairs.hpp"
 
 namespace la {
 
@@ -167,6 +170,50 @@ __global__ void k_pack_win(const uint8_t* __restrict__ genome, const uint8_t* __
 #pragma unroll
         for (int f = 0; f < ITEMS; ++f)
             code |= ((seq[f] != nullptr && j >= 1 && j <= ln.ls[f]) ? (uint32_t)seq[f][j - 1] : ROW_PAD) << (16 * f);
+        rowcodes[wv.row_off + rowidx(j, lane)] = code;
+    }
+}
+
+// k_pack for pairs whose reference and sequence are both slices of bytes in HBM (la_align_pairs_device): either side is reversed
+// and complemented in the gather where its flag is set
+template <int ITEMS>
+__global__ void k_pack_pairs(const uint8_t* __restrict__ bytes, const la_pair* __restrict__ pairs, const Lane* __restrict__ lanes,
+                             const Wave* __restrict__ waves, uint32_t* __restrict__ refcodes, uint32_t* __restrict__ rowcodes)
+{
+    const int w = blockIdx.x;
+    const Wave wv = waves[w];
+    const int lane = threadIdx.x & 63;
+    const Lane ln = lanes[(int64_t)w * WAVE + lane];
+    const uint8_t* ref[2] = {nullptr, nullptr};
+    const uint8_t* seq[2] = {nullptr, nullptr};
+    int32_t rrc[2] = {0, 0}, src[2] = {0, 0};
+#pragma unroll
+    for (int f = 0; f < ITEMS; ++f)
+        if (ln.out[f] >= 0) {
+            const la_pair pr = pairs[ln.out[f]];
+            ref[f] = bytes + pr.ref_off;
+            seq[f] = bytes + pr.seq_off;
+            rrc[f] = pr.ref_rc;
+            src[f] = pr.seq_rc;
+        }
+    for (int i = threadIdx.x >> 6; i < wv.nch * W; i += blockDim.x >> 6) {
+        uint32_t code = 0;
+#pragma unroll
+        for (int f = 0; f < ITEMS; ++f) {
+            uint32_t c = REF_PAD;
+            if (ref[f] != nullptr && i < ln.lr[f]) c = rrc[f] ? complement((uint32_t)ref[f][ln.lr[f] - 1 - i]) : (uint32_t)ref[f][i];
+            code |= c << (16 * f);
+        }
+        refcodes[wv.ref_off + (int64_t)i * WAVE + lane] = code;
+    }
+    for (int j = threadIdx.x >> 6; j < wv.rows4; j += blockDim.x >> 6) {
+        uint32_t code = 0;
+#pragma unroll
+        for (int f = 0; f < ITEMS; ++f) {
+            uint32_t c = ROW_PAD;
+            if (seq[f] != nullptr && j >= 1 && j <= ln.ls[f]) c = src[f] ? complement((uint32_t)seq[f][ln.ls[f] - j]) : (uint32_t)seq[f][j - 1];
+            code |= c << (16 * f);
+        }
         rowcodes[wv.row_off + rowidx(j, lane)] = code;
     }
 }
@@ -373,6 +420,7 @@ struct Group {
 
 inline int32_t ref_len(const la_item& it) { return it.ref_len; }
 inline int32_t ref_len(const la_window& wd) { return wd.pad_left + wd.slice_len + wd.pad_right; }
+inline int32_t ref_len(const la_pair& pr) { return pr.ref_len; }
 
 template <class Item>
 void add_wave(Group& g, const Params& prm, const Item* items, const int32_t* min_score, const int64_t* order, int64_t n, int items_per_lane)
@@ -417,9 +465,10 @@ void add_wave(Group& g, const Params& prm, const Item* items, const int32_t* min
 // Everything after the checks of the entry points: the 16-bit / int32 split, launch groups within the scratch budget, and per
 // group the pack step, then k_la16 or k_la32.  The items (la_item or la_window) and the pool go to the device as given;
 // pack(items_per_lane, n_waves, d_pool, d_items, d_lanes, d_waves, d_ref, d_row) launches the step that fills a group's codes.
+// With d_scores_out (n_items int32 in device memory) the kernels store there and nothing comes down into `scores`.
 template <class Item, class Pack>
 int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const uint8_t* pool, int64_t pool_len, const Item* items,
-                int64_t n_items, const int32_t* min_score, int32_t* scores, la_timing& tm, Pack pack)
+                int64_t n_items, const int32_t* min_score, int32_t* scores, la_timing& tm, Pack pack, int32_t* d_scores_out = nullptr)
 {
     if (n_items == 0) return DSA_OK;
     HIPL(hipSetDevice(device));
@@ -460,7 +509,8 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
     DeviceBuffer<unsigned long long> d_row_groups;      // what k_la16 swept in this call
     HIPL(d_pool.reserve((size_t)pool_len));
     HIPL(d_items.reserve((size_t)n_items));
-    HIPL(d_scores.reserve((size_t)n_items));
+    if (!d_scores_out) HIPL(d_scores.reserve((size_t)n_items));
+    int32_t* const d_scores_p = d_scores_out ? d_scores_out : d_scores.p;
     HIPL(d_row_groups.reserve(1));
     HIPL(hipMemset(d_row_groups.p, 0, sizeof(unsigned long long)));
     if (pool_len > 0) HIPL(hipMemcpy(d_pool.p, pool, (size_t)pool_len, hipMemcpyHostToDevice));
@@ -499,10 +549,10 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
             const unsigned grid = hiphost::grid_of(n_waves, WG_WAVES);
             if (items_per_lane == 2)
                 hipLaunchKernelGGL(k_la16, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
-                                   d_bnd.p, prm, d_scores.p, d_row_groups.p);
+                                   d_bnd.p, prm, d_scores_p, d_row_groups.p);
             else
                 hipLaunchKernelGGL(k_la32, dim3(grid), dim3(WG_WAVES * WAVE), 0, nullptr, d_lanes.p, d_waves.p, n_waves, d_ref.p, d_row.p,
-                                   d_bnd.p, prm, d_scores.p);
+                                   d_bnd.p, prm, d_scores_p);
             HIPL(hipEventRecord(ev[2], nullptr));
             HIPL(hipEventSynchronize(ev[2]));
             HIPL(hipGetLastError());
@@ -517,7 +567,7 @@ int align_items(int device, int32_t match, int32_t mismatch, int32_t gap, const 
     int rc = run_range(0, first16, 1);
     if (rc == DSA_OK) rc = run_range(first16, n_items, 2);
     if (rc != DSA_OK) return rc;
-    HIPL(hipMemcpy(scores, d_scores.p, (size_t)n_items * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (!d_scores_out) HIPL(hipMemcpy(scores, d_scores.p, (size_t)n_items * sizeof(int32_t), hipMemcpyDeviceToHost));
     unsigned long long row_groups = 0;
     HIPL(hipMemcpy(&row_groups, d_row_groups.p, sizeof row_groups, hipMemcpyDeviceToHost));
     tm.row_groups16 = (int32_t)std::min<unsigned long long>(row_groups, (unsigned long long)INT32_MAX);
@@ -626,3 +676,33 @@ int la_align_windows_min(const la_genome* genome, int32_t match, int32_t mismatc
 }
 
 }  // extern "C"
+
+// la_pairs.hpp.  The checks of la_align_windows_min, on pairs.
+__attribute__((visibility("hidden"))) int la_align_pairs_device(int device, const uint8_t* d_bytes, int64_t bytes_len, int32_t match, int32_t mismatch,
+                                                                int32_t gap, const la_pair* pairs, int64_t n_pairs, const int32_t* min_score,
+                                                                int32_t* d_scores, la_timing* timing)
+{
+    const auto t_begin = std::chrono::steady_clock::now();
+    la_timing tm{};
+    if (n_pairs < 0 || (n_pairs > 0 && (!pairs || !d_scores || !d_bytes))) return fail(g_err, DSA_E_ARG, "null argument");
+    if (n_pairs >= (int64_t)1 << 31) return fail(g_err, DSA_E_LIMIT, "more than 2^31-1 pairs");
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const la_pair& pr = pairs[k];
+        if (pr.ref_len < 0 || pr.seq_len < 0 || pr.ref_off < 0 || pr.seq_off < 0 || pr.ref_off + pr.ref_len > bytes_len || pr.seq_off + pr.seq_len > bytes_len)
+            return fail(g_err, DSA_E_ARG, "pair %lld lies outside the bytes", (long long)k);
+        tm.cells += ((int64_t)pr.ref_len + 1) * ((int64_t)pr.seq_len + 1);
+    }
+    const int rc = align_items(device, match, mismatch, gap, nullptr, 0, pairs, n_pairs, min_score, nullptr, tm,
+                               [d_bytes](int items_per_lane, int n_waves, const uint8_t*, const la_pair* d_pairs, const Lane* d_lanes, const Wave* d_waves,
+                                         uint32_t* d_ref, uint32_t* d_row) {
+                                   if (items_per_lane == 2)
+                                       hipLaunchKernelGGL(k_pack_pairs<2>, dim3(n_waves), dim3(256), 0, nullptr, d_bytes, d_pairs, d_lanes, d_waves, d_ref, d_row);
+                                   else
+                                       hipLaunchKernelGGL(k_pack_pairs<1>, dim3(n_waves), dim3(256), 0, nullptr, d_bytes, d_pairs, d_lanes, d_waves, d_ref, d_row);
+                               },
+                               d_scores);
+    if (rc != DSA_OK) return rc;
+    tm.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (timing) *timing = tm;
+    return DSA_OK;
+}

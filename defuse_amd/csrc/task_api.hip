@@ -700,3 +700,14 @@ __attribute__((visibility("hidden"))) int taskstore_create_device(int device, co
     *out = s;
     return DSA_OK;
 }
+
+// For conc_api.hip: where the sequences of a reference lie (device pointers, valid as long as it lives).
+__attribute__((visibility("hidden"))) void task_reference_device(const task_reference* r, int* device, const uint8_t** bytes, int64_t* bytes_len,
+                                                                 const task_seq** seqs, int64_t* n_seqs)
+{
+    *device = r->device;
+    *bytes = r->bytes.p;
+    *bytes_len = r->bytes_len;
+    *seqs = r->seqs.p;
+    *n_seqs = r->n_seqs;
+}

@@ -440,6 +440,7 @@ struct taskc_ctx {
     DeviceBuffer<uint8_t, GrowSize> rout;
     int64_t rout_bytes = 0;
     bool has_regions = false;
+    int64_t n_groups = 0;       // of the regions text, -1 if it is the dedup text's
     // small device-to-host copies land here
     u64 h_u64 = 0;
     uint32_t h_u32 = 0;
@@ -700,6 +701,7 @@ int regions_run(taskc_ctx* c, bool from_dedup, taskc_result* r)
     r->n_lines = q;
     if (q == 0) {
         c->has_regions = true;
+        c->n_groups = from_dedup ? -1 : 0;
         return DSA_OK;
     }
     const bool parsed_before = c->parsed;
@@ -772,6 +774,7 @@ int regions_run(taskc_ctx* c, bool from_dedup, taskc_result* r)
     c->timing.print_ms = hiphost::elapsed(c->ev[10], c->ev[11]);
     c->rout_bytes = out_bytes;
     c->has_regions = true;
+    c->n_groups = from_dedup ? -1 : n_groups;
     r->n_clusters = sum.n_ids;
     r->out_bytes = out_bytes;
     return DSA_OK;
@@ -946,4 +949,26 @@ __attribute__((visibility("hidden"))) int taskc_lines_device(taskc_ctx* c, bool 
     *out = taskc_lines_view{c->device, c->text.p, c->lstart.p, c->llen.p, c->rec.p, from_dedup ? c->osrc.p : nullptr, c->n_lines,
                             from_dedup ? c->dout_lines : c->n_lines};
     return DSA_OK;
+}
+
+// For conc_api.hip: the groups by (id, end) that taskc_regions(TASKC_INPUT) last made, in key order: the key (id, end, either with
+// the sign bit turned), the least start, the greatest end and the input line that is the group's last.  Device pointers, valid
+// until the next call on the taskc_ctx.  DSA_E_ARG unless the regions text is the input's.
+__attribute__((visibility("hidden"))) int taskc_groups_device(taskc_ctx* c, taskc_groups_view* out)
+{
+    if (!c->has_regions || c->n_groups < 0) return TASKC_FAIL(DSA_E_ARG, "the ctx has no regions text of its input (taskc_regions(TASKC_INPUT) first)");
+    *out = taskc_groups_view{c->k64[0].p, c->gmin.p, c->gmax.p, c->glast.p, c->n_groups};
+    return DSA_OK;
+}
+
+// For conc_api.hip (conc_into_taskc): a piece from this device's memory, as taskc_add_cover adds one.
+__attribute__((visibility("hidden"))) int taskc_add_device(taskc_ctx* c, int device, const uint8_t* text, int64_t len)
+{
+    if (device != c->device) return TASKC_FAIL(DSA_E_ARG, "the ctx and the text are on devices %d and %d", c->device, device);
+    if (len > (int64_t)INT32_MAX) return TASKC_FAIL(DSA_E_LIMIT, "a text of %lld bytes, more than 2^31 - 1", (long long)len);
+    if (len == 0) return DSA_OK;
+    drop_outputs(c);
+    const int rc = add_piece(c, text, len, hipMemcpyDeviceToDevice);
+    if (rc != DSA_OK) (void)hipStreamSynchronize(c->st);
+    return rc;
 }

@@ -93,6 +93,15 @@ struct taskc_lines_view {
     int64_t n_input_lines, n_lines;
 };
 
+// The groups of taskc_regions over the input (taskc_api.hip: taskc_groups_device; conc_api.hip).
+struct taskc_groups_view {
+    const unsigned long long* key;      // ((id ^ sign bit) << 32) | (end ^ sign bit), ascending
+    const int32_t* gmin;
+    const int32_t* gmax;
+    const uint32_t* glast;
+    int64_t n_groups;
+};
+
 // bytes of v in plain decimal
 TASKC_HD int taskc_dec_len(int32_t v)
 {

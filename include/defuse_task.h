@@ -436,6 +436,189 @@ int taskc_parse_regions(taskc_ctx* ctx, taskt_ctx* into, const taskt_names* seq_
 int taskc_get_timing(const taskc_ctx* ctx, taskc_timing* out);
 const char* taskc_last_error(void);
 
+/* ---- concordant clusters ------------------------------------------------------------------------------------------------
+ * The concordant-cluster filter on cluster text in device memory (conc_*, defuse_amd/csrc/conc_api.hip).
+ *
+ * Between the set cover and the duplicate filter the pipeline drops every cluster whose two ends can be explained by one
+ * locus (scripts/defuse_run.pl:484-505):
+ *
+ *     prep_local_alignment_seqs.pl -r FASTA -g GTF -c clusters.sc.unfilt -s 2000     > clusters.sc.local.seq
+ *     localalign -m 10 -x -5 -g -5 -t 0.8                                            > clusters.sc.local.align
+ *     cat clusters.sc.unfilt | filter_column.pl clusters.sc.local.align 0 1
+ *
+ * This section replaces the three steps in one call sequence over a taskc_ctx that holds clusters.sc.unfilt (taskc_add or
+ * taskc_add_cover) and a task_reference that holds the FASTA; no sequence byte crosses the bus:
+ *
+ *     conc_models_create   once per run: the gene models, flattened by the host reader (defuse_amd/concfilter.py)
+ *     conc_targets         every cluster end's targets: the genomic window, and one window per transcript of every
+ *                          overlapping gene in whose coding sequence or UTR the genomic midpoint lies
+ *     conc_align           SimpleAligner of every window against the other end's whole extent (la_api.hip's kernels)
+ *     conc_filter          the clusters.sc.local.align text, and the cluster lines of the ids it does not name
+ *     conc_into_taskc      that text into a taskc_ctx, device to device: taskc_dedup follows
+ *
+ * Canonical order.  Perl prints clusters, genes and transcripts in hash order.  Here targets (and so the local.align lines)
+ * come by cluster id ascending, end 0 then 1, the genomic target first, then genes ascending by id bytes, then a gene's
+ * transcripts ascending by name bytes.  The filtered text is in file order, as filter_column.pl's.
+ *
+ * Positions are kept doubled ("half-units"), since (start + end) / 2 may end in .5; every test is on integers.
+ * Bio::DB::Fasta::subseq and caloffset are restated literally: `start ||= 1`, `stop ||= length`, the swap with reverse and
+ * complement when start > stop, each bound minus 1 clamped to [0, L - 1] and truncated.  A window is clipped, not padded.
+ *
+ * Where this section stops and the scripts do not (conc_result.stop_kind; nothing is output on a stop):
+ *   - a line with fewer than eight fields or with a field 0, 1, 6 or 7 that taskc_regions does not read as an integer
+ *     (CONC_FEW_FIELDS, CONC_BAD_INTEGER, the line in stop_line): Perl takes any text as a key and numifies the coordinates,
+ *     and filter_column.pl dies only on a line without field 0;
+ *   - a cluster id whose ends are not exactly 0 and 1 (CONC_NOT_TWO_ENDS, the id in stop_value): Perl dies on a missing end
+ *     0 or 1 and ignores ends with other numbers;
+ *   - a strand that is neither "+" nor "-" (CONC_BAD_STRAND): Perl treats it as a minus strand that equals no transcript's;
+ *   - an empty reference name (CONC_EMPTY_NAME): Perl dies in the bins of the null transcript's chromosome;
+ *   - an other end whose name the FASTA lacks (CONC_NO_OTHER_SEQ): Perl dies at the first target of that end that prints,
+ *     and not at all if none does;
+ *   - an other end on a sequence without bytes (CONC_EMPTY_OTHER): the maximum score is 0 and localalign prints "-nan".
+ * DSA_E_LIMIT: a name of the form `name:a-b` (subseq would cut it), a coordinate beyond +-TASK_MAX_COORD, a range outside
+ * [0, TASK_MAX_PARAM], a target on a sequence without bytes, more than 2^31 - 1 targets.  A stop is reported first.
+ *
+ * Host round trips: the counts that size a buffer (targets, kept targets, bytes of either text, the first stop) and, in
+ * conc_align, one 32-byte pair per target down (the wave planner of la_api.hip reads the lengths) and up again with the
+ * lanes and waves it plans.  Scores stay on the device.
+ *
+ * Out of scope: select_fusion_clusters.pl (its nearest gene among equally near ones is Perl's hash order, so its output is
+ * no function of its input); a defuse_glue step and a C++ GTF reader (the tools keep their paths); the
+ * clusters.sc.local.seq text itself (the descriptors stand for it); more than one GPU.  There is no CPU path.
+ */
+#define CONC_FEW_FIELDS     1      /* = TASKC_FEW_FIELDS                                                            */
+#define CONC_BAD_INTEGER    2      /* = TASKC_BAD_INTEGER                                                           */
+#define CONC_NOT_TWO_ENDS   3
+#define CONC_BAD_STRAND     4
+#define CONC_EMPTY_NAME     5
+#define CONC_NO_OTHER_SEQ   6
+#define CONC_EMPTY_OTHER    7
+
+#define CONC_ALIGN_TEXT     0      /* conc_fetch: clusters.sc.local.align                                           */
+#define CONC_FILTERED       1      /* conc_fetch: the cluster lines that stay                                       */
+
+#define CONC_KIND_GENOMIC     0
+#define CONC_KIND_TRANSCRIPT  1
+
+typedef struct conc_gene {
+    int32_t start, end;             /* the region: [least first-exon start, greatest last-sorted-exon end]           */
+    int32_t tx_first, tx_count;     /* its transcripts: gene_tx[tx_first ..), ascending by name bytes                */
+} conc_gene;
+
+typedef struct conc_transcript {
+    int32_t gene, chrom;
+    int32_t strand;                 /* 0 "+", 1 "-", 2 anything else                                                 */
+    int32_t exon_first, exon_count; /* exons[..], stably sorted by start                                             */
+    int32_t expr_first, expr_count; /* expressed[..]: CDS, 5' UTR and 3' UTR pieces                                  */
+    int32_t pad_;
+} conc_transcript;
+
+typedef struct conc_interval {
+    int32_t start, end;
+} conc_interval;
+
+typedef struct conc_name {
+    int64_t off;                    /* names[off .. off + len)                                                       */
+    int32_t len;
+    int32_t pad_;
+} conc_name;
+
+/* Host arrays, copied by conc_models_create.  Genes are numbered ascending by id bytes; chrom_names and transcript_names
+ * ascend strictly by their bytes; chrom_genes[chrom_gene_first[c] .. chrom_gene_first[c + 1]) are the genes an accepted
+ * line put on chromosome c, ascending by region start; seq_names[k] names sequence k of the task_reference. */
+typedef struct conc_models_desc {
+    const conc_gene*       genes;
+    const int32_t*         gene_tx;
+    const conc_transcript* transcripts;
+    const conc_interval*   exons;
+    const conc_interval*   expressed;
+    const int32_t*         chrom_gene_first;   /* n_chroms + 1 */
+    const int32_t*         chrom_genes;
+    const uint8_t*         names;
+    const conc_name*       chrom_names;
+    const conc_name*       transcript_names;
+    const conc_name*       seq_names;
+    int64_t n_genes, n_gene_tx, n_transcripts, n_exons, n_expressed, n_chrom_genes, names_len, n_chroms, n_seqs;
+} conc_models_desc;
+
+/* One line of clusters.sc.local.seq: field 1 is sequence `seq` [start, start + len), reversed and complemented where revcomp
+ * is set; field 2 is sequence other_seq [other_start, + other_len), likewise by other_rev.  0-based, clipped. */
+typedef struct conc_target {
+    int32_t cluster_id, cluster_end;
+    int32_t kind;                   /* CONC_KIND_*                                                                   */
+    int32_t name;                   /* transcript index; genomic: chromosome index, -1 for a name the models lack    */
+    int32_t seq, start, len, revcomp;
+    int32_t other_seq, other_start, other_len, other_rev;
+} conc_target;
+
+typedef struct conc_result {
+    int64_t n_lines;                /* cluster lines read                                                            */
+    int64_t n_clusters;
+    int64_t n_targets;
+    int64_t n_kept_targets;         /* conc_filter: lines of the local.align text                                    */
+    int64_t align_bytes;
+    int64_t n_hit_clusters;         /* ids the local.align text names                                                */
+    int64_t n_kept_lines;
+    int64_t out_bytes;
+    int64_t n_noncanonical;         /* cluster lines whose id text is not the plain decimal of its value ("007", "+7"):
+                                       Perl's string keys tell such ids apart, this section compares values          */
+    int64_t stop_line;              /* 1-based, 0 where the stop is not at a line                                    */
+    int64_t stop_value;             /* the cluster id of a stop at a cluster                                         */
+    int32_t stop_kind;              /* 0 or CONC_*                                                                   */
+    int32_t stop_field;             /* -1 or the field of a CONC_BAD_INTEGER                                         */
+} conc_result;
+
+/* HIP-event times of the last call of each stage. */
+typedef struct conc_timing {
+    float   targets_ms;             /* groups (taskc_regions), count, scan, emit                                     */
+    float   sort_ms;                /* canonical order                                                               */
+    float   download_ms;            /* the descriptors to the wave planner                                           */
+    float   pack_ms;                /* k_pack_pairs                                                                  */
+    float   dp_ms;                  /* k_la16 / k_la32                                                               */
+    float   print_ms;               /* decide, lengths, scan, the local.align text                                   */
+    float   filter_ms;              /* hit ids, line lengths, scan, gather                                           */
+    float   pad_;
+    int64_t cells;
+    int64_t n_packed16, n_int32;
+} conc_timing;
+
+typedef struct conc_models conc_models;
+typedef struct conc_ctx conc_ctx;
+
+/* DSA_E_ARG, before a device is touched, for an index outside its table, name tables that do not ascend, a negative count;
+ * DSA_E_LIMIT for a `name:a-b` name or a coordinate beyond +-TASK_MAX_COORD. */
+int conc_models_create(int device, const conc_models_desc* desc, conc_models** out);
+void conc_models_destroy(conc_models* models);
+
+int conc_create(int device, conc_ctx** out);
+void conc_destroy(conc_ctx* ctx);
+
+/* The targets of the input text of `clusters`, whose groups by (id, end) it makes with taskc_regions(TASKC_INPUT): the
+ * regions text of `clusters` is that one afterwards.  reference must have models' n_seqs sequences.  The ctx reads the
+ * text of `clusters` in place until conc_filter has run: no other call on `clusters` in between. */
+int conc_targets(conc_ctx* ctx, taskc_ctx* clusters, const conc_models* models, const task_reference* reference, int32_t range,
+                 conc_result* result);
+int conc_fetch_targets(conc_ctx* ctx, conc_target* out, int64_t n);
+
+/* Scores of all targets.  match > 0; min_score of a pair is threshold_min_score(score_max(other_len, match), threshold), as
+ * bin/localalign derives it: a score below it is not exact.  DSA_E_ARG without targets of conc_targets. */
+int conc_align(conc_ctx* ctx, const task_reference* reference, int32_t match, int32_t mismatch, int32_t gap, double threshold,
+               conc_result* result);
+int conc_fetch_scores(conc_ctx* ctx, int32_t* out, int64_t n);
+
+/* Both texts, with the scores and the threshold of conc_align. */
+int conc_filter(conc_ctx* ctx, conc_result* result);
+int conc_fetch(conc_ctx* ctx, int32_t which, int64_t offset, uint8_t* buf, int64_t len);
+
+int conc_get_timing(const conc_ctx* ctx, conc_timing* out);
+const char* conc_last_error(void);
+
+/* The filtered text behind the text of `into` (another taskc_ctx than the one conc_targets read, or that one after
+ * taskc_begin), as taskc_add_cover does with a cover's output.  It is a conc_ function with the conc_ctx first, not a
+ * taskc_add_*: conc_api.hip implements it and its errors are conc_last_error()'s, and every taskc_* function of this header
+ * is bound by one module (defuse_amd/clusterregions.py) whose table the ABI check counts. */
+int conc_into_taskc(const conc_ctx* ctx, taskc_ctx* into);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@
 #include <unordered_set>
 #include <vector>
 
+#include "../defuse_amd/csrc/la_score.hpp"      // score_max, threshold_min_score: shared with the library's conc_api.hip
+
 namespace defuse {
 
 enum Strand { PlusStrand = 0, MinusStrand = 1 };   // tools/Common.h:20-24
@@ -1785,21 +1787,7 @@ inline bool AddReads(const std::string& filename, ReadStore& reads, std::ostream
 }
 
 // ---- scores against a percent-perfect threshold (tools/localalign.cpp:84-92, tools/matealign.cpp:191-201) ---------------------
-// maxScore = len(sequence) * match (a size_t product stored in an int), percent = (double) score / maxScore, and a line is printed
-// unless percent < threshold.
-inline int score_max(size_t seq_len, int matchScore) { return (int)(seq_len * (size_t)matchScore); }
-
-// the smallest score a line needs to be printed at all: below it the device may stop early (la_align_batch_min's min_score)
-inline int32_t threshold_min_score(int maxScore, double threshold)
-{
-    int32_t s = std::numeric_limits<int32_t>::min();
-    if (maxScore > 0 && threshold > 0.0) {
-        s = (int32_t)std::min<double>(std::ceil(threshold * (double)maxScore), 2147483000.0);
-        while (s > 0 && !((double)(s - 1) / (double)maxScore < threshold)) --s;     // exactly the test of the line filter
-        while ((double)s / (double)maxScore < threshold) ++s;
-    }
-    return s;
-}
+// score_max and threshold_min_score: defuse_amd/csrc/la_score.hpp, included above.
 
 // appends `id \t score \t percent` (operator<<(double): %g, six significant digits) unless percent < threshold
 inline void append_score_line(std::string& out, std::string_view id, int score, int maxScore, double threshold)
